@@ -8,8 +8,14 @@ Default workload (BASELINE.json configs[1], what the driver runs):
     2. decode: stripe s loses block e = s mod 14 and rebuilds it with jerasure_matrix_decode semantics
        (row_k_ones = failed_num, rs.cpp:36) into the rebuild buffer  (ecg_decode_batch, 14 patterns)
   value = N * S * 2 * k * B / t_max in GiB/s (each pass reads k data-sized blocks per stripe).
-  Inputs: splitmix64 bytes generated on the GPU before the timed region.
-  The same line also carries, after the headline's buffers are freed:
+  Inputs: splitmix64 bytes generated on the GPU before the timed region (a fixed seed: the same arguments give
+  the same bytes on every run).
+  A plain run sets up, warms up, times the steps and prints the headline line.  `--dump-outputs DIR` adds, after
+  the timed steps, DIR/parity.npy and DIR/rebuilt.npy: what the last step computed, as float32 (a fixed seeded
+  sample of each block's bytes at the default size), so that two builds can be compared output for output.
+  With `--full` the outputs are also verified (a re-decode with the erased blocks poisoned, parity checksums), the
+  roofline object names the committed PMC traffic and rocprofv3 summaries, the CPU baseline runs, and the same
+  line also carries, after the headline's buffers are freed:
     per_rank  every rank's encode / decode kernel time and HBM fraction (all-gathered);
     config5   BASELINE.json configs[4] at this N: RS(10,4), 4 MiB, 65536 stripes sharded over the ranks
               in HBM-resident waves of 1024 -- aggregate GiB/s, every rank's HBM fraction, and the
@@ -94,6 +100,15 @@ def parse():
     ap.add_argument("--self-p2p", action="store_true",
                     help="lrc-repair-ring at N = 1: rank 0 sends the partials to itself over RCCL point to point "
                          "(the N > 1 nccl code path on one GPU; the rate is an intra-GPU copy, not xGMI)")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: after the headline, also verify its outputs (poisoned re-decode, parity "
+                         "checksums), run the line's other objects (config 5, host path, configs 3 / 4, families, "
+                         "ring objects; each has its own --no-* switch) and the CPU baselines.  Without it the run "
+                         "sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default workload: after the timed steps write what the last step computed (the parity "
+                         "blocks and the rebuilt blocks, or a fixed seeded sample of their bytes when they exceed "
+                         "the size cap) as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration")
     ap.add_argument("--launch-check", action="store_true",
@@ -390,6 +405,37 @@ def cpu_baseline(k, m, B, target_s):
     return line
 
 
+# ------------------------------------------------------------------------------- --dump-outputs
+
+DUMP_MAX_BYTES = 32 << 20  # all the files of one rank together
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(directory, r, outputs):
+    """--dump-outputs: write each [rows][blocks][B] uint8 output of the timed path's last step as float32
+    <directory>/<name>.npy (rank q > 0 of a multi-GPU run: <name>.rank<q>.npy).  An output that fits its equal
+    share of DUMP_MAX_BYTES goes whole, as [rows][blocks][B]; of a larger one every block contributes the same
+    number of bytes, [rows][blocks][c]: its first and last byte and offsets drawn once per output from a generator
+    seeded with DUMP_SEED, so two runs with the same arguments dump the same positions."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_MAX_BYTES // 4 // len(outputs) - 64  # float32 elements per output, the .npy header allowed for
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+    for name, t in outputs.items():
+        rows, blocks, B = t.shape
+        c = min(B, share // (rows * blocks))
+        if c < 1:
+            raise SystemExit(f"bench.py: --dump-outputs: {name} has more blocks ({rows * blocks}) than the dump holds")
+        if c < B:
+            off = torch.randint(0, B, (rows * blocks, c), generator=gen)
+            off[:, 0] = 0
+            off[:, -1] = B - 1
+            blk = torch.arange(rows * blocks, device=t.device)[:, None]  # t may be a strided view: index, no copy
+            t = t[blk // blocks, blk % blocks, off.to(t.device)].view(rows, blocks, c)
+        suffix = f".rank{r.rank}" if r.rank else ""
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), t.to(torch.float32).cpu().numpy())
+
+
 # ------------------------------------------------------------------------------- config 2 (default)
 
 def rs_encode_decode(a, r):
@@ -426,18 +472,22 @@ def rs_encode_decode(a, r):
     # the timed steps follow the warm-up with no idle gap (the clocks drop within tens of ms of idle,
     # DESIGN.md §4); the outputs are checked after them -- every step rewrites the same bytes
     elapsed, evs = timed_loop(r, a.steps, step)
-    idx = torch.arange(S, device="cuda")
-    # outside the timing: the timed decodes rebuilt the erased blocks, and one more decode with every erased
-    # block POISONED rebuilds the same bytes (so the kernel neither reads nor copies the block it rebuilds)
-    erased = stripes[idx, idx % n].clone()
-    assert torch.equal(rebuilt[:, 0], erased), "decode mismatch"
-    stripes[idx, idx % n] = 0xA5
-    rebuilt.zero_()
-    ecg.decode_batch(k, m, M, 1, patterns, stripes, out=rebuilt, pattern_of_stripe=pattern_of_stripe)
-    assert torch.equal(rebuilt[:, 0], erased), "decode mismatch with the erased blocks poisoned"
-    stripes[idx, idx % n] = erased
-    del erased
-    checks = D.gather_checksums(D.checksum64(coding.contiguous()), r, device="cuda")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, r, {"parity": coding, "rebuilt": rebuilt})
+    checks = None
+    if a.full:
+        idx = torch.arange(S, device="cuda")
+        # outside the timing: the timed decodes rebuilt the erased blocks, and one more decode with every erased
+        # block POISONED rebuilds the same bytes (so the kernel neither reads nor copies the block it rebuilds)
+        erased = stripes[idx, idx % n].clone()
+        assert torch.equal(rebuilt[:, 0], erased), "decode mismatch"
+        stripes[idx, idx % n] = 0xA5
+        rebuilt.zero_()
+        ecg.decode_batch(k, m, M, 1, patterns, stripes, out=rebuilt, pattern_of_stripe=pattern_of_stripe)
+        assert torch.equal(rebuilt[:, 0], erased), "decode mismatch with the erased blocks poisoned"
+        stripes[idx, idx % n] = erased
+        del erased, idx
+        checks = D.gather_checksums(D.checksum64(coding.contiguous()), r, device="cuda")
     enc_ms = [e[0].elapsed_time(e[1]) for e in evs]
     dec_ms = [e[1].elapsed_time(e[2]) for e in evs]
     enc_avg = sum(enc_ms) / len(enc_ms) / 1e3
@@ -460,19 +510,22 @@ def rs_encode_decode(a, r):
         "roofline": {"bound": "hbm", "kernel": "gf_vec_kernel<MT=4,STRIDED> (encode)",
                      "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": pmc_traffic("encode", f"rs{k}{m}_B{B}_S{S}"),
-                     "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE "
-                                       "passes of this bench command (FETCH x2, KiB -> B, per launch), committed "
-                                       "with the round's profiles; not measured inside this run",
                      "algorithmic_bytes_per_launch": enc_bytes,
                      "decode_achieved": round(dec_bytes / dec_avg / 1e9, 1),
                      "decode_frac": round(dec_bytes / dec_avg / 1e9 / HBM_PEAK_GBS, 4),
-                     "decode_traffic": pmc_traffic("decode", f"rs{k}{m}_B{B}_S{S}"),
-                     "frac_source": "HIP events on this run's stream, averaged over the timed steps",
-                     **committed_profile()},
-        "parity_checksums": [f"{c:016x}" for c in checks],
+                     "frac_source": "HIP events on this run's stream, averaged over the timed steps"},
         "build": build_provenance(),
     }
+    if a.full:
+        # the committed PMC traffic and rocprofv3 summaries beside this run's fractions; the verified outputs' sums
+        line["roofline"].update({
+            "traffic": pmc_traffic("encode", f"rs{k}{m}_B{B}_S{S}"),
+            "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE "
+                              "passes of this bench command (FETCH x2, KiB -> B, per launch), committed "
+                              "with the round's profiles; not measured inside this run",
+            "decode_traffic": pmc_traffic("decode", f"rs{k}{m}_B{B}_S{S}"),
+            **committed_profile()})
+        line["parity_checksums"] = [f"{c:016x}" for c in checks]
     # every rank's own kernel times and HBM fractions (HIP events on its stream), not rank 0's only
     mine = [enc_avg * 1e3, dec_avg * 1e3, achieved / HBM_PEAK_GBS, dec_bytes / dec_avg / 1e9 / HBM_PEAK_GBS]
     per = D.gather_floats(mine, r, device="cuda")
@@ -482,8 +535,10 @@ def rs_encode_decode(a, r):
                         "encode_frac_max": round(max(x[2] for x in per), 4),
                         "decode_frac_min": round(min(x[3] for x in per), 4),
                         "decode_frac_max": round(max(x[3] for x in per), 4)}
+    if not a.full:
+        return line
     # the headline's buffers go before config 5 allocates its wave
-    del arena, stripes, rebuilt, data, coding, pattern_of_stripe, idx, step, evs
+    del arena, stripes, rebuilt, data, coding, pattern_of_stripe, step, evs
     torch.cuda.empty_cache()
     def optional():
         if not a.no_config5:

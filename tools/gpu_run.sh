@@ -5,9 +5,9 @@
 #   tests      GPU parity suite (-m gpu, one process, per-test thread timeout)  -> pytest_gpu.log
 #   test:<k>   GPU tests matching -k <k>                                          -> pytest_<k>.log
 #   smoke      __graft_entry__.smoke()                                            -> smoke.log
-#   bench      default bench line (python bench.py)                               -> bench.log
-#   headline   bench line of the headline alone (no config 5 / ring / host path)  -> bench_headline.log
-#   prof       rocprofv3 --kernel-trace --stats of the default line and of the headline alone
+#   bench      full bench line (python bench.py --full)                           -> bench.log
+#   headline   bench line of the headline alone (a plain run, without --full)     -> bench_headline.log
+#   prof       rocprofv3 --kernel-trace --stats of the full line and of the headline alone
 #   profh      the headline alone only (r06: the default line under rocprofv3 once died in the HIP runtime,
 #              SIGSEGV inside hipLaunchKernel, during config 3's 8-thread per-call form)
 #   pmc        FETCH_SIZE and WRITE_SIZE passes of the headline -> pmc_traffic.json (tools/parse_pmc.py)
@@ -82,10 +82,10 @@ for step in "$@"; do
            timeout -k 10 600 $PYT tests -v -s -m gpu -k "$k" > "$L" 2>&1; rc=$?
            tail -3 "$L"; echo "test $k rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     smoke) run smoke 300 "$O/smoke.log" python -c "import __graft_entry__ as g; g.smoke()"; tail -1 "$O/smoke.log" ;;
-    bench) run bench 500 "$O/bench.log" python bench.py; tail -1 "$O/bench.log" | cut -c1-400 ;;
+    bench) run bench 500 "$O/bench.log" python bench.py --full; tail -1 "$O/bench.log" | cut -c1-400 ;;
     headline) run headline 400 "$O/bench_headline.log" python bench.py --no-cpu-baseline $HEADLINE
            tail -1 "$O/bench_headline.log" | cut -c1-400 ;;
-    prof) prof prof prof.log --steps 40 --warmup 3 --no-cpu-baseline
+    prof) prof prof prof.log --full --steps 40 --warmup 3 --no-cpu-baseline
           rm -f "$O/prof/run_kernel_trace.csv"  # 10^5 rows (config 3's per-call forms): the stats stay
           prof prof_headline prof_headline.log --steps 40 --warmup 3 --no-cpu-baseline $HEADLINE ;;
     profh) prof prof_headline prof_headline.log --steps 40 --warmup 3 --no-cpu-baseline $HEADLINE ;;
