@@ -93,6 +93,11 @@ int ecg_traffic_counters(long long* launches, long long* bytes) {
     return ECG_OK;
 }
 
+int ecg_launch_histogram(long long* counts, int cap) {
+    if (cap < 0 || (cap > 0 && !counts)) return ECG_EINVAL;
+    return launch_histogram(counts, cap);
+}
+
 int ecg_set_option(int option, long long value) { return set_option(option, value) == 0 ? ECG_OK : ECG_EINVAL; }
 long long ecg_get_option(int option) { return get_option(option); }
 

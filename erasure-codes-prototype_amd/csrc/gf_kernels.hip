@@ -991,6 +991,34 @@ void launch_traffic(long long* launches, long long* bytes) {
     if (bytes) *bytes = g_moved.load(std::memory_order_relaxed);
 }
 
+// Launch histogram (ecg_launch_histogram): one counter per kernel instantiation launch_gf can dispatch, bumped
+// where the instantiation is picked -- one relaxed add per kernel launch, beside the two above.  Slot layout:
+// include/ecg.h (ECG_HIST_*); the GfMode values are the header's mode numbers.
+static_assert(GF_MODE_INLINE == 0 && GF_MODE_PTRS == 1 && GF_MODE_STRIDED == 2 && GF_MODE_INLINE_LAT == 3,
+              "ECG_HIST_* slots are laid out by these mode numbers");
+static_assert(kMaxMTBin == 16 && kMaxMT <= kMaxMTBin, "ECG_HIST_* slots hold 16 tile widths");
+std::atomic<long long> g_hist[ECG_HIST_SLOTS] = {};
+
+static void hist_vec(int mode, int binary, int nt, int MT) {
+    g_hist[ECG_HIST_VEC + (((mode * 2 + (binary ? 1 : 0)) * 4 + (nt & 3)) * 16 + (MT - 1))].fetch_add(
+        1, std::memory_order_relaxed);
+}
+
+static void hist_byte(int mode, int binary, int MT) {  // mode: INLINE (also for INLINE_LAT calls), PTRS or STRIDED
+    g_hist[ECG_HIST_BYTE + ((mode * 2 + (binary ? 1 : 0)) * 16 + (MT - 1))].fetch_add(1, std::memory_order_relaxed);
+}
+
+static void hist_lat(int binary, int MT, int k, long long B) {  // the bucket of pick_lat_k, EAGER of lat_dword_launch
+    const int kb = k <= 4 ? 0 : k <= 6 ? 1 : k <= 8 ? 2 : k <= 10 ? 3 : k <= 12 ? 4 : 5;
+    g_hist[ECG_HIST_LAT + ((((binary ? 1 : 0) * 8 + (MT - 1)) * 6 + kb) * 2 + (B <= kLatEagerBytes ? 1 : 0))].fetch_add(
+        1, std::memory_order_relaxed);
+}
+
+int launch_histogram(long long* counts, int cap) {
+    for (int i = 0; counts && i < cap && i < ECG_HIST_SLOTS; i++) counts[i] = g_hist[i].load(std::memory_order_relaxed);
+    return ECG_HIST_SLOTS;
+}
+
 hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st, int* n_wg) {
     if (n_wg) *n_wg = 0;
     if (base.k < 1 || base.m < 1 || base.S < 1 || base.B < 0 || base.MT < 1 ||
@@ -1011,6 +1039,7 @@ hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st
         const long long gx = ((a.B >> 2) + kLatThreads - 1) / kLatThreads;
         Launcher l = a.binary ? pick_lat_dword_bin<true>(a.MT, a.k) : pick_lat_dword_bin<false>(a.MT, a.k);
         if (!l) return hipErrorInvalidValue;
+        hist_lat(a.binary, a.MT, a.k, a.B);
         const hipError_t e = l(a, dim3((unsigned)gx), st);
         if (e != hipSuccess) return e;
         if (n_wg) *n_wg = (int)gx;
@@ -1044,6 +1073,7 @@ hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st
         }
         if (!l) return hipErrorInvalidValue;
         if (a.done_flags && (mode != GF_MODE_INLINE_LAT || vec_bytes < a.B)) return hipErrorInvalidValue;
+        hist_vec(mode, a.binary, nt, a.MT);
         const hipError_t e = l(a, dim3((unsigned)gx, (unsigned)a.rtiles), st);
         if (e != hipSuccess) return e;
         if (n_wg) *n_wg = (int)(gx * a.rtiles);
@@ -1068,6 +1098,7 @@ hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st
             default: return hipErrorInvalidValue;
         }
         if (!l) return hipErrorInvalidValue;
+        hist_byte(mode == GF_MODE_INLINE_LAT ? (int)GF_MODE_INLINE : mode, a.binary, a.MT);
         const hipError_t e = l(a, dim3((unsigned)gx, (unsigned)a.rtiles), st);
         if (e != hipSuccess) return e;
     }

@@ -128,6 +128,9 @@ int set_option(int opt, long long value);
 hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t stream, int* n_wg = nullptr);
 // Region-product kernels launch_gf has launched in this process, and the bytes they move as planned.
 void launch_traffic(long long* launches, long long* bytes);
+// Launches per kernel instantiation (include/ecg.h ecg_launch_histogram): fills counts[0, min(cap, ECG_HIST_SLOTS))
+// and returns ECG_HIST_SLOTS.
+int launch_histogram(long long* counts, int cap);
 
 // Deterministic synthetic bytes: 8-byte word w = splitmix64(seed + (word_offset + w) * golden).
 hipError_t launch_fill_splitmix(void* dst, long long nbytes, unsigned long long seed,

@@ -71,7 +71,7 @@ EXPORTS = [
     "ecg_jerasure_invert_matrix", "ecg_jerasure_matrix_multiply", "ecg_galois_region_xor",
     "ecg_jerasure_matrix_encode", "ecg_jerasure_matrix_decode", "ecg_jerasure_matrix_dotprod",
     "ecg_batch_begin", "ecg_batch_flush", "ecg_batch_end", "ecg_batch_defer_host", "ecg_batch_scratch",
-    "ecg_batch_last_stats", "ecg_traffic_counters",
+    "ecg_batch_last_stats", "ecg_traffic_counters", "ecg_launch_histogram",
     "ecg_dev_matrix_encode", "ecg_dev_matrix_decode", "ecg_matrix_apply_batch", "ecg_matrix_apply_batch_multi",
     "ecg_encode_batch",
     "ecg_decode_batch", "ecg_perform_addition_batch", "ecg_make_decode_matrix", "ecg_region_xor_batch", "ecg_encode_batch_host", "ecg_decode_batch_host",
@@ -167,6 +167,7 @@ def lib():
         "ecg_batch_scratch": ([P, ctypes.c_size_t], I),
         "ecg_batch_last_stats": ([ctypes.POINTER(LL)] * 4, I),
         "ecg_traffic_counters": ([ctypes.POINTER(LL)] * 2, I),
+        "ecg_launch_histogram": ([ctypes.POINTER(LL), I], I),
         "ecg_device_count": ([], I),
         "ecg_set_device": ([I], I),
         "ecg_free": ([P], None),
@@ -408,6 +409,39 @@ def traffic_counters():
     v = [ctypes.c_longlong(0) for _ in range(2)]
     _check(lib().ecg_traffic_counters(*[ctypes.byref(x) for x in v]), "traffic_counters")
     return {"launches": v[0].value, "bytes": v[1].value}
+
+
+ECG_HIST_VEC, ECG_HIST_BYTE, ECG_HIST_LAT, ECG_HIST_SLOTS = 0, 512, 608, 800  # include/ecg.h
+LAT_BUCKETS = (4, 6, 8, 10, 12, 16)  # input-count buckets of the latency kernel
+
+
+def hist_key(slot):
+    """The kernel instantiation a histogram slot counts (include/ecg.h ECG_HIST_*):
+    ("vec", mode, bin, nt, MT), ("byte", mode, bin, MT) or ("lat", bin, MT, KB, eager)."""
+    if slot < ECG_HIST_BYTE:
+        rest, mt = divmod(slot - ECG_HIST_VEC, 16)
+        rest, nt = divmod(rest, 4)
+        mode, b = divmod(rest, 2)
+        return ("vec", mode, b, nt, mt + 1)
+    if slot < ECG_HIST_LAT:
+        rest, mt = divmod(slot - ECG_HIST_BYTE, 16)
+        mode, b = divmod(rest, 2)
+        return ("byte", mode, b, mt + 1)
+    rest, eager = divmod(slot - ECG_HIST_LAT, 2)
+    rest, kb = divmod(rest, 6)
+    b, mt = divmod(rest, 8)
+    return ("lat", b, mt + 1, LAT_BUCKETS[kb], eager)
+
+
+def launch_histogram():
+    """Process-wide {kernel instantiation key (hist_key): launches so far}, instantiations never launched left
+    out.  The counts sum to traffic_counters()["launches"]."""
+    n = lib().ecg_launch_histogram(None, 0)
+    if n != ECG_HIST_SLOTS:
+        raise EcgError(ECG_EINVAL, f"launch_histogram: library has {n} slots, binding {ECG_HIST_SLOTS}")
+    v = (ctypes.c_longlong * n)()
+    _check(lib().ecg_launch_histogram(v, n), "launch_histogram")
+    return {hist_key(i): c for i, c in enumerate(v) if c}
 
 
 def dev_matrix_encode(k, m, matrix, data, coding, B, stream=None):

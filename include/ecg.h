@@ -233,6 +233,27 @@ int ecg_batch_last_stats(long long* recorded, long long* composed, long long* la
  * difference over a region of calls is the traffic those calls executed (bench.py's executed bytes; PMC
  * FETCH/WRITE counters agree where measured).  Either pointer may be NULL. */
 int ecg_traffic_counters(long long* launches, long long* bytes);
+/* Process-wide launch histogram since the library loaded (diagnostics; test coverage of the dispatcher): one
+ * counter per region-product kernel instantiation, bumped once per kernel launch, so the sum over all slots
+ * moves with ecg_traffic_counters' `launches`.  Fills counts[0, min(cap, ECG_HIST_SLOTS)) and returns
+ * ECG_HIST_SLOTS; counts may be NULL when cap is 0.  Slots, with bin = 1 for the BINARY flavour (every
+ * coefficient 0 or 1), MT = output rows per row tile (1..8, BINARY up to 16), mode = 0 pointers in the kernel
+ * arguments, 1 pointer tables, 2 strided batch, 3 kernel-argument pointers with every input load issued up
+ * front (small single calls):
+ *   16-byte-column kernel: ECG_HIST_VEC  + ((mode * 2 + bin) * 4 + nt) * 16 + (MT - 1)
+ *                          nt = the ECG_OPT_NT policy the launch ran with (0..3; tiles wider than 8 always 3)
+ *   byte kernel:           ECG_HIST_BYTE + (mode * 2 + bin) * 16 + (MT - 1)
+ *                          mode 0..2 (a mode-3 call's tail runs the mode-0 kernel)
+ *   4-byte-column latency kernel:
+ *                          ECG_HIST_LAT  + (((bin * 8 + (MT - 1)) * 6 + kb) * 2 + eager
+ *                          kb = input-count bucket 0..5 for k <= 4, 6, 8, 10, 12, 16; eager = 1 for blocks of
+ *                          at most 16 KiB
+ * Slots of combinations that are not built (a wide tile at nt != 3, a GENERAL tile wider than 8) stay 0. */
+#define ECG_HIST_VEC 0
+#define ECG_HIST_BYTE 512
+#define ECG_HIST_LAT 608
+#define ECG_HIST_SLOTS 800
+int ecg_launch_histogram(long long* counts, int cap);
 /* Generic region product: out[dst_ids[p]] = XOR_j coef[p*k_in+j] * in[src_ids[j]] for S stripes,
  * in block b of stripe s at in_base + s*in_sstride + b*in_bstride (likewise out). */
 int ecg_matrix_apply_batch(int k_in, int m_out, const int* coef, const int* src_ids, const int* dst_ids,
