@@ -6,14 +6,11 @@
 #include <vector>
 
 #include "../../include/ecg.h"
+#include "capi_handle.hpp"
 #include "codes.hpp"
 #include "engine.hpp"
 
 using namespace ecg;
-
-struct ecg_ec {
-    ErasureCode* impl;
-};
 
 namespace {
 
@@ -448,6 +445,15 @@ int ecg_ec_m(const ecg_ec* ec) { return ec ? ec->impl->m : ECG_EINVAL; }
 int ecg_ec_make_encoding_matrix(ecg_ec* ec, int* final_matrix) {
     if (!ec || !final_matrix) return ECG_EINVAL;
     return ec->impl->make_encoding_matrix(final_matrix);
+}
+
+int ecg_ec_check_matrix(ecg_ec* ec, int* H, int cap) {
+    if (!ec || cap < 0) return ECG_EINVAL;
+    std::vector<int> h;
+    const int rows = ec->impl->check_matrix(h);
+    if (rows < 0) return rows;
+    if (H && cap >= (int)h.size()) memcpy(H, h.data(), h.size() * sizeof(int));
+    return rows;
 }
 
 int ecg_ec_check_if_decodable(ecg_ec* ec, const int* failure_idxs, int n) {

@@ -60,6 +60,20 @@ void ErasureCode::get_coding_parameters(CodingParameters& cp) const {  // erasur
     cp.local_or_column = local_or_column;
 }
 
+int ErasureCode::check_matrix(std::vector<int>& H) {
+    if (k < 1 || m < 1) return ECG_EINVAL;
+    std::vector<int> M((size_t)k * m, 0);
+    if (const int rc = make_encoding_matrix(M.data()); rc != ECG_OK) return rc;
+    const size_t n = (size_t)k + m;
+    H.assign((size_t)m * n, 0);
+    for (int p = 0; p < m; p++) {
+        bool any = false;
+        for (int j = 0; j < k; j++) any |= (H[p * n + j] = M[(size_t)p * k + j] & 0xff) != 0;
+        if (any) H[p * n + k + p] = 1;  // jerasure_matrix_dotprod leaves the block of an all-zero row untouched
+    }
+    return m;
+}
+
 namespace {
 
 uint64_t hash_ints(const std::vector<int>& v) {
@@ -1034,29 +1048,54 @@ std::vector<std::vector<int>> ProductCode::block_map() const {
 
 // The row codes, then the column codes over the data and the row parities (pc.cpp:39-76), planned as one call
 // and composed (finish_plan): each data block is read once, the row parities are not re-read.
+int ProductCode::plan_encode_steps(Plan& p) {
+    for (int i = 0; i < k2; i++) {
+        std::vector<int> d(k1), c(m1);
+        for (int j = 0; j < k1; j++) d[j] = i * k1 + j;
+        for (int j = 0; j < m1; j++) c[j] = k + i * m1 + j;
+        if (int r = rowc().plan_encode(p, d, c); r != ECG_OK) return r;
+    }
+    for (int i = 0; i < k1 + m1; i++) {
+        std::vector<int> d(k2), c(m2);
+        for (int j = 0; j < k2; j++) d[j] = i < k1 ? j * k1 + i : k + j * m1 + i - k1;
+        for (int j = 0; j < m2; j++)
+            c[j] = i < k1 ? k + k2 * m1 + j * k1 + i : k + k2 * m1 + k1 * m2 + j * m1 + i - k1;
+        if (int r = colc().plan_encode(p, d, c); r != ECG_OK) return r;
+    }
+    return ECG_OK;
+}
+
 int ProductCode::encode(char** data_ptrs, char** coding_ptrs, int block_size) {
     thread_local std::vector<int> key;
     key.assign({4});
     state_key(key);
     const CallPlan* cp = nullptr;
-    const int rc = run_planned(key, [&](Plan& p) {
-        for (int i = 0; i < k2; i++) {
-            std::vector<int> d(k1), c(m1);
-            for (int j = 0; j < k1; j++) d[j] = i * k1 + j;
-            for (int j = 0; j < m1; j++) c[j] = k + i * m1 + j;
-            if (int r = rowc().plan_encode(p, d, c); r != ECG_OK) return r;
-        }
-        for (int i = 0; i < k1 + m1; i++) {
-            std::vector<int> d(k2), c(m2);
-            for (int j = 0; j < k2; j++) d[j] = i < k1 ? j * k1 + i : k + j * m1 + i - k1;
-            for (int j = 0; j < m2; j++)
-                c[j] = i < k1 ? k + k2 * m1 + j * k1 + i : k + k2 * m1 + k1 * m2 + j * m1 + i - k1;
-            if (int r = colc().plan_encode(p, d, c); r != ECG_OK) return r;
-        }
-        return (int)ECG_OK;
-    }, cp);
+    const int rc = run_planned(key, [&](Plan& p) { return plan_encode_steps(p); }, cp);
     if (rc != ECG_OK) return rc;
     return run(cp->ops, data_ptrs, k, coding_ptrs, m, block_size);
+}
+
+// One row per coding block, taken from the step that writes it: a column code over row parities reads the row
+// parities themselves, so a corrupt data block fails its row's check and its column's, not the composed ones.
+int ProductCode::check_matrix(std::vector<int>& H) {
+    if (k < 1 || m < 1) return ECG_EINVAL;
+    Plan p;
+    if (const int rc = plan_encode_steps(p); rc != ECG_OK) return rc;
+    const size_t n = (size_t)k + m;
+    H.assign((size_t)m * n, 0);
+    for (const LinearOp& op : p.ops)
+        for (int r = 0; r < op.m_out(); r++) {
+            const int d = op.dst_ids[r];
+            if (d < k || d >= (int)n) return ECG_EINVAL;
+            int* row = &H[(size_t)(d - k) * n];
+            for (int j = 0; j < op.k_in(); j++) {
+                const int sid = op.src_ids[j];
+                if (sid < 0 || sid >= (int)n) return ECG_EINVAL;
+                row[sid] = op.coef[(size_t)r * op.k_in() + j];
+            }
+            row[d] = 1;
+        }
+    return m;
 }
 
 // Iterative control flow of pc.cpp:79-195 (and HVPC pc.cpp:921-1029 with ncols = k1, nrows = k2).
@@ -1295,26 +1334,28 @@ void HVPC::init_coding_parameters(const CodingParameters& cp) {  // pc.cpp:869-8
     m = k1 * m2 + k2 * m1;
 }
 
+int HVPC::plan_encode_steps(Plan& p) {
+    for (int i = 0; i < k2; i++) {
+        std::vector<int> d(k1), c(m1);
+        for (int j = 0; j < k1; j++) d[j] = i * k1 + j;
+        for (int j = 0; j < m1; j++) c[j] = k + i * m1 + j;
+        if (int r = row_code.plan_encode(p, d, c); r != ECG_OK) return r;
+    }
+    for (int i = 0; i < k1; i++) {
+        std::vector<int> d(k2), c(m2);
+        for (int j = 0; j < k2; j++) d[j] = j * k1 + i;
+        for (int j = 0; j < m2; j++) c[j] = k + k2 * m1 + j * k1 + i;
+        if (int r = col_code.plan_encode(p, d, c); r != ECG_OK) return r;
+    }
+    return ECG_OK;
+}
+
 int HVPC::encode(char** data_ptrs, char** coding_ptrs, int block_size) {  // pc.cpp:890-918
     thread_local std::vector<int> key;
     key.assign({4});
     state_key(key);
     const CallPlan* cp = nullptr;
-    const int rc = run_planned(key, [&](Plan& p) {
-        for (int i = 0; i < k2; i++) {
-            std::vector<int> d(k1), c(m1);
-            for (int j = 0; j < k1; j++) d[j] = i * k1 + j;
-            for (int j = 0; j < m1; j++) c[j] = k + i * m1 + j;
-            if (int r = row_code.plan_encode(p, d, c); r != ECG_OK) return r;
-        }
-        for (int i = 0; i < k1; i++) {
-            std::vector<int> d(k2), c(m2);
-            for (int j = 0; j < k2; j++) d[j] = j * k1 + i;
-            for (int j = 0; j < m2; j++) c[j] = k + k2 * m1 + j * k1 + i;
-            if (int r = col_code.plan_encode(p, d, c); r != ECG_OK) return r;
-        }
-        return (int)ECG_OK;
-    }, cp);
+    const int rc = run_planned(key, [&](Plan& p) { return plan_encode_steps(p); }, cp);
     if (rc != ECG_OK) return rc;
     return run(cp->ops, data_ptrs, k, coding_ptrs, m, block_size);
 }

@@ -66,6 +66,11 @@ public:
     virtual int decode(char** data_ptrs, char** coding_ptrs, int block_size, int* erasures, int failed_num) = 0;
     virtual int check_if_decodable(const std::vector<int>& failure_idxs) = 0;  // 1, 0, or < 0
     virtual int make_encoding_matrix(int* final_matrix) = 0;
+    // The check this class's encode establishes (include/ecg.h ecg_ec_check_matrix): H is m x (k + m), row p
+    // holding the coefficients of the encode step that writes coding block p over the blocks that step reads,
+    // and 1 at k + p; a coding block no step writes (an all-zero matrix row) gets an all-zero row.  Returns m
+    // or a negative code.  Host only.  Here: [make_encoding_matrix | I].
+    virtual int check_matrix(std::vector<int>& H);
     int encode_partial_blocks_for_encoding(char** data_ptrs, char** coding_ptrs, int block_size,
                                            std::vector<int> data_idxs, std::vector<int> parity_idxs);
     int encode_partial_blocks_for_decoding(char** data_ptrs, char** coding_ptrs, int block_size,
@@ -335,6 +340,7 @@ public:
     int decode(char** data_ptrs, char** coding_ptrs, int block_size, int* erasures, int failed_num) override;
     int check_if_decodable(const std::vector<int>& failure_idxs) override;
     int make_encoding_matrix(int*) override { return ECG_OK; }  // pc.h:37: empty
+    int check_matrix(std::vector<int>& H) override;  // from the uncomposed row and column steps of encode
     int partial_encoding_matrix(std::vector<int> data_idxs, std::vector<int> parity_idxs,
                                 std::vector<int>& out) override;
     int partial_decoding_matrix(std::vector<int> lsi, std::vector<int> si, std::vector<int> fi,
@@ -356,6 +362,8 @@ protected:
     virtual RSCode& partial_col() { return col_code; }  // code used by partial calls (local_or_column)
     virtual RSCode& partial_row() { return row_code; }
     virtual bool has_global() const { return true; }
+    // The steps of encode, one op per row / column code, in the order the reference runs them (uncomposed)
+    virtual int plan_encode_steps(Plan& p);
     int plan_iterative_decode(Plan& plan, int* erasures, int failed_num, int ncols, int nrows);
     // plan_iterative_decode through the per-thread call-plan cache, composed (codes.cpp finish_plan), and run
     int decode_iterative(char** data_ptrs, char** coding_ptrs, int block_size, int* erasures, int failed_num,
@@ -393,6 +401,7 @@ public:
 
 protected:
     bool has_global() const override { return false; }
+    int plan_encode_steps(Plan& p) override;
 };
 
 // metadata.cpp:48-77

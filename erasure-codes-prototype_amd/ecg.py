@@ -78,7 +78,7 @@ EXPORTS = [
     "ecg_fill_random",
     "ecg_ec_factory", "ecg_ec_destroy", "ecg_ec_init_coding_parameters", "ecg_ec_get_coding_parameters",
     "ecg_ec_set_memory", "ecg_ec_set_isvertical", "ecg_ec_k", "ecg_ec_m", "ecg_ec_make_encoding_matrix",
-    "ecg_ec_check_if_decodable", "ecg_ec_encode", "ecg_ec_decode",
+    "ecg_ec_check_matrix", "ecg_ec_check_if_decodable", "ecg_ec_encode", "ecg_ec_decode",
     "ecg_ec_encode_partial_blocks_for_encoding", "ecg_ec_encode_partial_blocks_for_decoding",
     "ecg_ec_perform_addition", "ecg_ec_encode_partial_blocks_for_decoding_with_addition",
     "ecg_ec_encode_partial_blocks_for_encoding_with_addition",
@@ -203,6 +203,7 @@ def lib():
         "ecg_ec_k": ([P], I),
         "ecg_ec_m": ([P], I),
         "ecg_ec_make_encoding_matrix": ([P, IP], I),
+        "ecg_ec_check_matrix": ([P, IP, I], I),
         "ecg_ec_check_if_decodable": ([P, IP, I], I),
         "ecg_ec_encode": ([P, PP, PP, I], I),
         "ecg_ec_decode": ([P, PP, PP, I, IP, I], I),
@@ -633,6 +634,14 @@ class ErasureCode:
         out = (ctypes.c_int * max(1, rows * self.k))()
         _check(lib().ecg_ec_make_encoding_matrix(self._h, out), "make_encoding_matrix")
         return list(out)
+
+    def check_matrix(self):
+        """ecg_ec_check_matrix: the m x (k + m) check the class's encode establishes, as a list of rows (what
+        ecg_scrub.ec_batch runs on the GPU)."""
+        n = self.k + self.m
+        out = (ctypes.c_int * max(1, self.m * n))()
+        rows = _check(lib().ecg_ec_check_matrix(self._h, out, self.m * n), "check_matrix")
+        return [list(out[p * n:(p + 1) * n]) for p in range(rows)]
 
     def check_if_decodable(self, failure_idxs):
         return _check(lib().ecg_ec_check_if_decodable(self._h, _ints(failure_idxs), len(failure_idxs)),

@@ -338,6 +338,12 @@ int ecg_ec_set_isvertical(ecg_ec* ec, int isvertical); /* HPC::isvertical (pc.h:
 int ecg_ec_k(const ecg_ec* ec);
 int ecg_ec_m(const ecg_ec* ec);
 int ecg_ec_make_encoding_matrix(ecg_ec* ec, int* final_matrix); /* m x k, where the class defines one */
+/* The check the class's encode establishes: m rows over the stripe's k+m blocks; row p has the coefficients of the
+ * encode step that writes coding block p over the blocks THAT STEP reads (for product codes the column code over the
+ * row parities reads row parities, so a corrupt block shows in its row's and its column's checks), and 1 at k+p.
+ * A coding block no step writes (an all-zero matrix row) has an all-zero row.  Host only: no kernel runs.
+ * Returns m, or a negative code; H written when cap >= m*(k+m).  libecg_scrub.so (ecg_scrub.h) runs it on the GPU. */
+int ecg_ec_check_matrix(ecg_ec* ec, int* H, int cap);
 int ecg_ec_check_if_decodable(ecg_ec* ec, const int* failure_idxs, int n);
 int ecg_ec_encode(ecg_ec* ec, char** data_ptrs, char** coding_ptrs, int block_size);
 int ecg_ec_decode(ecg_ec* ec, char** data_ptrs, char** coding_ptrs, int block_size, int* erasures, int failed_num);
