@@ -1,0 +1,200 @@
+// extern "C" entry points declared in include/ecg_locate.h (libecg_locate.so): the host side of corruption
+// localisation.  A locate reads two table sets, both LinearOps kept by the engine's program cache
+// (Engine::program_set: built once per distinct H, uploaded, retired only when no launch can still read them): the
+// check itself, as the scrub builds it (check_common.hpp make_check), and the candidate ratios
+// H[q][b] / H[p0(b)][b] as an r x n "product" whose tables the kernel reads by candidate (locate_kernels.hpp).
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/ecg_locate.h"
+#include "capi_handle.hpp"
+#include "check_common.hpp"
+#include "engine.hpp"
+#include "gf256.hpp"
+#include "locate_kernels.hpp"
+
+using namespace ecg;
+
+namespace {
+
+struct Plan {
+    Check chk;
+    LinearOp ratio;  // r x n: H[q][b] / H[p0(b)][b]; an all-zero column for a zero column of H
+    unsigned p0[kInlineSrc / 8];
+    int n = 0, r = 0;
+};
+
+Plan make_plan(int n, int r, const int* H, const int* src_ids, bool consecutive) {
+    Plan pl;
+    pl.n = n;
+    pl.r = r;
+    pl.chk = make_check(n, r, H, src_ids, consecutive);
+    pl.ratio.src_ids = iota(n);
+    pl.ratio.dst_ids = iota(r);
+    pl.ratio.coef.assign((size_t)r * n, 0);
+    memset(pl.p0, 0, sizeof(pl.p0));
+    for (int b = 0; b < n; b++) {
+        int p0 = 0;
+        while (p0 < r && (H[(size_t)p0 * n + b] & 0xff) == 0) p0++;
+        pl.p0[b >> 3] |= (p0 < r ? (unsigned)p0 : kNoPivot) << ((b & 7) * 4);
+        if (p0 == r) continue;
+        const int lead = H[(size_t)p0 * n + b] & 0xff;
+        for (int q = p0; q < r; q++) pl.ratio.coef[(size_t)q * n + b] = (uint8_t)gf::div(H[(size_t)q * n + b], lead);
+    }
+    return pl;
+}
+
+int too_large(long long n, int r) {
+    set_last_error("locate: r = " + std::to_string(r) + ", n = " + std::to_string(n) + " exceeds r <= " +
+                   std::to_string(kMaxMT) + ", n <= " + std::to_string(kInlineSrc) +
+                   " (one lane holds all r syndromes); product codes stay with ecg_scrub_suspects");
+    return ECG_EINVAL;
+}
+
+// Flush the thread's batch scope, fetch both table sets, zero the votes, launch.  `fill` sets the launch's sources.
+template <class Fill>
+int run_locate(const Plan& pl, int mode, long long B, int S, const int* d_stripe_ids, unsigned* d_votes, bool vec_ok,
+               hipStream_t st, Fill fill) {
+    if (const int rc = batch_flush_pending(); rc != ECG_OK) return rc;
+    Engine& eng = Engine::instance();
+    int status = ECG_OK;
+    std::shared_ptr<ProgramSet> ps = eng.program_set(&pl.chk.op, 1, &status, st);
+    if (!ps) return status;
+    std::shared_ptr<ProgramSet> rs = eng.program_set(&pl.ratio, 1, &status, st);
+    if (!rs) return status;
+    if (const int rc = ps->ensure_ready(st); rc != ECG_OK) return rc;
+    if (const int rc = rs->ensure_ready(st); rc != ECG_OK) return rc;
+    if (ps->MT != pl.r || ps->rtiles != 1 || rs->MT != pl.r || rs->rtiles != 1 || rs->k != pl.n) return ECG_EINVAL;
+    LocateLaunch a;
+    memset(&a, 0, sizeof(a));
+    a.g.tabs = ps->d_tabs;
+    a.g.src_ids = ps->d_src;
+    a.g.dst_ids = ps->d_dst;
+    a.g.stripe_of = d_stripe_ids;
+    a.g.B = B;
+    a.g.k = ps->k;
+    a.g.m = ps->m;
+    a.g.S = S;
+    a.g.MT = ps->MT;
+    a.g.rtiles = ps->rtiles;
+    a.g.binary = 0;  // the GENERAL flavour always: the tables of 0 and 1 are exact
+    a.votes = d_votes;
+    a.ident = pl.chk.ident;
+    a.ident_base = pl.chk.ident_base;
+    a.ratios = rs->d_tabs;
+    a.n = pl.n;
+    memcpy(a.p0, pl.p0, sizeof(a.p0));
+    fill(a.g);
+    if (const hipError_t e = hipMemsetAsync(d_votes, 0, (size_t)S * (size_t)(pl.n + 2) * sizeof(unsigned), st);
+        e != hipSuccess)
+        return hip_fail(e, "hipMemsetAsync(locate votes)");
+    if (const hipError_t e = launch_locate(a, mode, vec_ok, st); e != hipSuccess) return hip_fail(e, "launch_locate");
+    eng.note_launch(*ps, st);
+    eng.note_launch(*rs, st);
+    return ECG_OK;
+}
+
+int run_strided_locate(const Plan& pl, const void* d_base, long long sstride, long long bstride, long long B,
+                       const int* d_stripe_ids, int S, unsigned* d_votes, hipStream_t st) {
+    const bool vec_ok = aligned16(d_base) && sstride % 16 == 0 && bstride % 16 == 0;
+    return run_locate(pl, GF_MODE_STRIDED, B, S, d_stripe_ids, d_votes, vec_ok, st, [&](GfLaunch& g) {
+        g.in_base = (const uint8_t*)d_base;
+        g.in_sstride = sstride;
+        g.in_bstride = bstride;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int ecg_locate_matrix_batch(int n, int r, const int* H, const int* src_ids, const void* d_base, long long sstride,
+                            long long bstride, long long B, const int* d_stripe_ids, int S_sel, unsigned* d_votes,
+                            void* stream) {
+    if (n < 1 || r < 1 || bad_sizes(B, S_sel) || !H || !src_ids || !d_base || !d_votes) return ECG_EINVAL;
+    if (r > kMaxMT || n > kInlineSrc) return too_large(n, r);
+    if (S_sel == 0 || B == 0) return ECG_OK;
+    return run_strided_locate(make_plan(n, r, H, src_ids, true), d_base, sstride, bstride, B, d_stripe_ids, S_sel,
+                              d_votes, (hipStream_t)stream);
+}
+
+int ecg_locate_encode_batch(int k, int m, const int* matrix, const void* d_stripes, long long sstride,
+                            long long bstride, long long B, const int* d_stripe_ids, int S_sel, unsigned* d_votes,
+                            void* stream) {
+    if (k < 1 || m < 1 || bad_sizes(B, S_sel) || !matrix || !d_stripes || !d_votes) return ECG_EINVAL;
+    if (m > kMaxMT || k > kInlineSrc - m) return too_large((long long)k + m, m);
+    if (S_sel == 0 || B == 0) return ECG_OK;
+    const std::vector<int> H = encode_check(k, m, matrix), ids = iota(k + m);
+    return run_strided_locate(make_plan(k + m, m, H.data(), ids.data(), true), d_stripes, sstride, bstride, B,
+                              d_stripe_ids, S_sel, d_votes, (hipStream_t)stream);
+}
+
+int ecg_locate_ec_batch(ecg_ec* ec, const void* d_stripes, long long sstride, long long bstride, long long B,
+                        const int* d_stripe_ids, int S_sel, unsigned* d_votes, void* stream) {
+    if (!ec || bad_sizes(B, S_sel) || !d_stripes || !d_votes || ec->impl->mem != ECG_MEM_DEVICE) return ECG_EINVAL;
+    std::vector<int> H;
+    const int r = ec->impl->check_matrix(H);
+    if (r < 0) return r;
+    if (r < 1) return ECG_EINVAL;
+    const int n = (int)(H.size() / (size_t)r);
+    if (r > kMaxMT || n > kInlineSrc) return too_large(n, r);
+    if (S_sel == 0 || B == 0) return ECG_OK;
+    const std::vector<int> ids = iota(n);
+    return run_strided_locate(make_plan(n, r, H.data(), ids.data(), true), d_stripes, sstride, bstride, B,
+                              d_stripe_ids, S_sel, d_votes, (hipStream_t)stream);
+}
+
+int ecg_locate_ec(ecg_ec* ec, char** d_data_ptrs, char** d_coding_ptrs, int block_size, unsigned* d_votes) {
+    if (!ec || block_size < 0 || !d_data_ptrs || !d_coding_ptrs || !d_votes || ec->impl->mem != ECG_MEM_DEVICE)
+        return ECG_EINVAL;
+    std::vector<int> H;
+    const int r = ec->impl->check_matrix(H);
+    if (r < 0) return r;
+    if (r < 1) return ECG_EINVAL;
+    const int k = ec->impl->k, n = (int)(H.size() / (size_t)r);
+    if (r > kMaxMT || n > kInlineSrc) return too_large(n, r);
+    for (int b = 0; b < n; b++)
+        if (!(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k])) return ECG_EINVAL;
+    if (block_size == 0) return ECG_OK;
+    bool vec_ok = true;
+    for (int b = 0; b < n; b++) vec_ok &= aligned16(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k]);
+    const std::vector<int> ids = iota(n);
+    return run_locate(make_plan(n, r, H.data(), ids.data(), false), GF_MODE_INLINE, block_size, 1, nullptr, d_votes,
+                      vec_ok, ec->impl->stream, [&](GfLaunch& g) {
+                          for (int b = 0; b < n; b++)
+                              g.isrc[b] = (const uint8_t*)(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k]);
+                      });
+}
+
+int ecg_locate_verdict(int n, const unsigned* h_votes, int* ids, int cap, int* n_ids) {
+    if (n < 1 || !h_votes || cap < 0 || (cap > 0 && !ids)) return ECG_EINVAL;
+    const unsigned bad = h_votes[n];
+    int voted = 0, full = 0, who = -1;
+    for (int b = 0; b < n; b++) {
+        if (h_votes[b] == 0) continue;
+        voted++;
+        if (h_votes[b] == bad) {
+            full++;
+            if (who < 0) who = b;
+        }
+    }
+    if (n_ids) *n_ids = voted;
+    if (voted > 0 && voted <= cap) {
+        int w = 0;
+        for (int b = 0; b < n; b++)
+            if (h_votes[b] != 0) ids[w++] = b;
+    }
+    if (bad == 0) return ECG_LOCATE_CLEAN;
+    if (full > 1) return ECG_LOCATE_AMBIGUOUS;
+    if (full == 1 && h_votes[n + 1] == 0) return who;
+    return ECG_LOCATE_MULTIPLE;
+}
+
+int ecg_locate_counters(long long* launches, long long* bytes) {
+    locate_traffic(launches, bytes);
+    return ECG_OK;
+}
+
+}  // extern "C"

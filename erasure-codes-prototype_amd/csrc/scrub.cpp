@@ -8,51 +8,13 @@
 
 #include "../../include/ecg_scrub.h"
 #include "capi_handle.hpp"
+#include "check_common.hpp"
 #include "engine.hpp"
 #include "scrub_kernels.hpp"
 
 using namespace ecg;
 
 namespace {
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-int hip_fail(hipError_t e, const char* what) {
-    set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-    return ECG_EHIP;
-}
-
-// A check as the kernels take it: the columns that go through the coefficient tables, as a LinearOp whose
-// "destinations" are the row numbers, and whether H = [C | I] (scrub_kernels.hpp ScrubLaunch::ident).
-struct Check {
-    LinearOp op;
-    int ident = 0, ident_base = 0;
-};
-
-// H = [C | I] when the last r of its columns are unit columns -- column kg + q a single 1 in row q -- over
-// consecutive blocks (`consecutive`: the strided form addresses them as ident_base + q), with C not empty.
-Check make_check(int k_in, int r, const int* H, const int* src_ids, bool consecutive) {
-    Check c;
-    const int kg = k_in - r;
-    bool ident = kg >= 1;
-    for (int q = 0; ident && q < r; q++) {
-        for (int p = 0; p < r; p++) ident &= (H[(size_t)p * k_in + kg + q] & 0xff) == (p == q ? 1 : 0);
-        ident &= !consecutive || src_ids[kg + q] == src_ids[kg] + q;
-    }
-    const int cols = ident ? kg : k_in;
-    c.ident = ident ? 1 : 0;
-    c.ident_base = ident ? src_ids[kg] : 0;
-    c.op.src_ids.assign(src_ids, src_ids + cols);
-    c.op.dst_ids.resize((size_t)r);
-    for (int p = 0; p < r; p++) c.op.dst_ids[p] = p;
-    c.op.coef.resize((size_t)cols * r);
-    for (int p = 0; p < r; p++)
-        for (int j = 0; j < cols; j++) c.op.coef[(size_t)p * cols + j] = (uint8_t)(H[(size_t)p * k_in + j] & 0xff);
-    return c;
-}
-
-// Sizes every entry point checks before anything else (and before any device is touched).
-bool bad_sizes(long long B, long long S) { return B < 0 || S < 0 || B >= (1LL << 31); }
 
 // Flush the thread's batch scope, fetch the tables, zero the counters, launch.  `fill` sets the launch's sources.
 template <class Fill>
@@ -97,24 +59,6 @@ int run_strided_check(const Check& chk, const void* d_base, long long sstride, l
         g.in_sstride = sstride;
         g.in_bstride = bstride;
     });
-}
-
-// [matrix | I] over k + m blocks; the row of an all-zero matrix row stays all zero (not checked)
-std::vector<int> encode_check(int k, int m, const int* matrix) {
-    const size_t n = (size_t)k + m;
-    std::vector<int> H((size_t)m * n, 0);
-    for (int p = 0; p < m; p++) {
-        bool any = false;
-        for (int j = 0; j < k; j++) any |= (H[p * n + j] = matrix[(size_t)p * k + j] & 0xff) != 0;
-        if (any) H[p * n + k + p] = 1;
-    }
-    return H;
-}
-
-std::vector<int> iota(int n) {
-    std::vector<int> v((size_t)n);
-    for (int i = 0; i < n; i++) v[i] = i;
-    return v;
 }
 
 }  // namespace
