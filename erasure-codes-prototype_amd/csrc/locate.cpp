@@ -197,4 +197,6 @@ int ecg_locate_counters(long long* launches, long long* bytes) {
     return ECG_OK;
 }
 
+int ecg_locate_last_launch(int* v, int cap) { return locate_last_launch(v, cap); }
+
 }  // extern "C"

@@ -307,12 +307,20 @@ Launcher pick(int R, int mode) {
 }
 
 std::atomic<long long> g_locate_launched{0}, g_locate_read{0};
+// geometry of the most recent vector-path launch (locate_kernels.hpp kLocateLaunchFields), all zero before the first
+std::atomic<int> g_locate_last[kLocateLaunchFields];
 
 }  // namespace
 
 void locate_traffic(long long* launches, long long* bytes) {
     if (launches) *launches = g_locate_launched.load(std::memory_order_relaxed);
     if (bytes) *bytes = g_locate_read.load(std::memory_order_relaxed);
+}
+
+int locate_last_launch(int* v, int cap) {
+    if (v && cap >= kLocateLaunchFields)
+        for (int i = 0; i < kLocateLaunchFields; ++i) v[i] = g_locate_last[i].load(std::memory_order_relaxed);
+    return kLocateLaunchFields;
 }
 
 hipError_t launch_locate(const LocateLaunch& base, int mode, bool vec_ok, hipStream_t st) {
@@ -348,6 +356,8 @@ hipError_t launch_locate(const LocateLaunch& base, int mode, bool vec_ok, hipStr
         if (gm == 2 && a.S % (8 * G) != 0) gm = 1;
         a.grid_map = (gm == 1 && gx % 8 == 0) ? 1 : (gm == 2) ? 2 : 0;
         a.map_group = (int)G;
+        const int geo[kLocateLaunchFields] = {a.grid_map, a.map_group, a.cols_per_wg, a.wg_per_stripe, a.S, a.rtiles};
+        for (int i = 0; i < kLocateLaunchFields; ++i) g_locate_last[i].store(geo[i], std::memory_order_relaxed);
         Launcher l = pick<false>(a.m, mode);
         if (!l) return hipErrorInvalidValue;
         const hipError_t e = l(sa, dim3((unsigned)gx), st);

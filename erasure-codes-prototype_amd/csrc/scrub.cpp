@@ -138,4 +138,6 @@ int ecg_scrub_counters(long long* launches, long long* bytes) {
     return ECG_OK;
 }
 
+int ecg_scrub_last_launch(int* v, int cap) { return scrub_last_launch(v, cap); }
+
 }  // extern "C"

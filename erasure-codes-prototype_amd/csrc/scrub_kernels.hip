@@ -261,12 +261,20 @@ Launcher pick(const GfLaunch& a, int mode) {
 }
 
 std::atomic<long long> g_scrub_launched{0}, g_scrub_read{0};
+// geometry of the most recent vector-path launch (scrub_kernels.hpp kScrubLaunchFields), all zero before the first
+std::atomic<int> g_scrub_last[kScrubLaunchFields];
 
 }  // namespace
 
 void scrub_traffic(long long* launches, long long* bytes) {
     if (launches) *launches = g_scrub_launched.load(std::memory_order_relaxed);
     if (bytes) *bytes = g_scrub_read.load(std::memory_order_relaxed);
+}
+
+int scrub_last_launch(int* v, int cap) {
+    if (v && cap >= kScrubLaunchFields)
+        for (int i = 0; i < kScrubLaunchFields; ++i) v[i] = g_scrub_last[i].load(std::memory_order_relaxed);
+    return kScrubLaunchFields;
 }
 
 hipError_t launch_scrub(const ScrubLaunch& base, int mode, bool vec_ok, hipStream_t st) {
@@ -303,6 +311,8 @@ hipError_t launch_scrub(const ScrubLaunch& base, int mode, bool vec_ok, hipStrea
         if (gm == 2 && a.S % (8 * G) != 0) gm = 1;
         a.grid_map = (gm == 1 && gx % 8 == 0) ? 1 : (gm == 2) ? 2 : 0;
         a.map_group = (int)G;
+        const int geo[kScrubLaunchFields] = {a.grid_map, a.map_group, a.cols_per_wg, a.wg_per_stripe, a.S, a.rtiles};
+        for (int i = 0; i < kScrubLaunchFields; ++i) g_scrub_last[i].store(geo[i], std::memory_order_relaxed);
         Launcher l = pick<false>(a, mode);
         if (!l) return hipErrorInvalidValue;
         const hipError_t e = l(sa, dim3((unsigned)gx, (unsigned)a.rtiles), st);

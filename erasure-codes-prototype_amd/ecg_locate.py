@@ -29,7 +29,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(ecg.LIB_PATH)), "libecg_
 # Every symbol include/ecg_locate.h declares (checked by tests/test_locate_host.py).
 EXPORTS = [
     "ecg_locate_matrix_batch", "ecg_locate_encode_batch", "ecg_locate_ec_batch", "ecg_locate_ec",
-    "ecg_locate_verdict", "ecg_locate_counters",
+    "ecg_locate_verdict", "ecg_locate_counters", "ecg_locate_last_launch",
 ]
 
 # ecg_locate_verdict statuses (a value >= 0 is a block id)
@@ -58,6 +58,7 @@ def lib():
         "ecg_locate_ec": ([P, PP, PP, I, P], I),
         "ecg_locate_verdict": ([I, UP, IP, I, IP], I),
         "ecg_locate_counters": ([ctypes.POINTER(LL)] * 2, I),
+        "ecg_locate_last_launch": ([IP, I], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -160,3 +161,18 @@ def counters():
     v = [ctypes.c_longlong(0) for _ in range(2)]
     _check(lib().ecg_locate_counters(*[ctypes.byref(x) for x in v]), "locate.counters")
     return {"launches": v[0].value, "bytes": v[1].value}
+
+
+LAST_LAUNCH_FIELDS = ("grid_map", "map_group", "cols_per_wg", "wg_per_stripe", "S", "rtiles")
+
+
+def last_launch():
+    """Geometry of the process's most recent vector-path locate launch, as placed in the launch descriptor after the
+    fallbacks (include/ecg_locate.h ecg_locate_last_launch): {grid_map, map_group, cols_per_wg, wg_per_stripe, S,
+    rtiles}, all zero before the first.  Byte-kernel launches do not change it."""
+    n = lib().ecg_locate_last_launch(None, 0)
+    if n != len(LAST_LAUNCH_FIELDS):
+        raise EcgError(ecg.ECG_EINVAL, f"locate.last_launch: library has {n} fields")
+    v = (ctypes.c_int * n)()
+    lib().ecg_locate_last_launch(v, n)
+    return dict(zip(LAST_LAUNCH_FIELDS, (int(x) for x in v)))

@@ -24,7 +24,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(ecg.LIB_PATH)), "libecg_
 # Every symbol include/ecg_scrub.h declares (checked by tests/test_scrub_host.py).
 EXPORTS = [
     "ecg_scrub_matrix_batch", "ecg_scrub_encode_batch", "ecg_scrub_ec_batch", "ecg_scrub_ec", "ecg_scrub_suspects",
-    "ecg_scrub_counters",
+    "ecg_scrub_counters", "ecg_scrub_last_launch",
 ]
 
 _L = None
@@ -50,6 +50,7 @@ def lib():
         "ecg_scrub_ec": ([P, PP, PP, I, P], I),
         "ecg_scrub_suspects": ([I, I, IP, UP, IP, I], I),
         "ecg_scrub_counters": ([ctypes.POINTER(LL)] * 2, I),
+        "ecg_scrub_last_launch": ([IP, I], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -133,3 +134,18 @@ def counters():
     v = [ctypes.c_longlong(0) for _ in range(2)]
     _check(lib().ecg_scrub_counters(*[ctypes.byref(x) for x in v]), "scrub.counters")
     return {"launches": v[0].value, "bytes": v[1].value}
+
+
+LAST_LAUNCH_FIELDS = ("grid_map", "map_group", "cols_per_wg", "wg_per_stripe", "S", "rtiles")
+
+
+def last_launch():
+    """Geometry of the process's most recent vector-path scrub launch, as placed in the launch descriptor after the
+    fallbacks (include/ecg_scrub.h ecg_scrub_last_launch): {grid_map, map_group, cols_per_wg, wg_per_stripe, S,
+    rtiles}, all zero before the first.  Byte-kernel launches do not change it."""
+    n = lib().ecg_scrub_last_launch(None, 0)
+    if n != len(LAST_LAUNCH_FIELDS):
+        raise EcgError(ecg.ECG_EINVAL, f"scrub.last_launch: library has {n} fields")
+    v = (ctypes.c_int * n)()
+    lib().ecg_scrub_last_launch(v, n)
+    return dict(zip(LAST_LAUNCH_FIELDS, (int(x) for x in v)))

@@ -91,6 +91,18 @@ int ecg_locate_ec(ecg_ec* ec, char** d_data_ptrs, char** d_coding_ptrs, int bloc
 int ecg_locate_verdict(int n, const unsigned* h_votes /* n+2 */, int* ids, int cap, int* n_ids);
 /* Locate kernels launched and bytes they read as planned, process-wide: S_sel * B * n per call. */
 int ecg_locate_counters(long long* launches, long long* bytes);
+/* Launch geometry of the most recent vector-path (16-byte column) locate launch, process-wide: a diagnostic that says
+ * which workgroup -> chunk map a call really ran, after the fallbacks of ECG_OPT_GRID_MAP, ECG_OPT_MAP_GROUP and
+ * ECG_OPT_COLS_PER_WG.  Six values, in order (those of ecg_scrub_last_launch):
+ *   v[0] grid_map       0 linear, 1 XCD-contiguous, 2 stripe groups per XCD
+ *   v[1] map_group      stripes per group, reduced to a power-of-two fraction of the option that divides S_sel / 8
+ *   v[2] cols_per_wg    16-byte columns per workgroup
+ *   v[3] wg_per_stripe  workgroups per selected stripe
+ *   v[4] S              S_sel, the launch stripes
+ *   v[5] rtiles         row tiles, always 1
+ * All zero before the first such launch; byte-kernel launches (tails, unaligned blocks) do not change it.  Host
+ * only.  Returns the number of values, 6; v is written when cap >= 6 (v may be NULL with cap == 0). */
+int ecg_locate_last_launch(int* v, int cap);
 
 #ifdef __cplusplus
 }

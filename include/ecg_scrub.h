@@ -51,6 +51,18 @@ int ecg_scrub_suspects(int r, int n, const int* H, const unsigned* h_counts, int
  * columns of H are unit columns over consecutive blocks (H = [C | I]: every encode check) only C goes through the
  * coefficient tables and each of those r blocks is read once, by its own row's tile: S*B*(tiles*(k_in-r) + r). */
 int ecg_scrub_counters(long long* launches, long long* bytes);
+/* Launch geometry of the most recent vector-path (16-byte column) scrub launch, process-wide: a diagnostic that says
+ * which workgroup -> chunk map a call really ran, after the fallbacks of ECG_OPT_GRID_MAP, ECG_OPT_MAP_GROUP and
+ * ECG_OPT_COLS_PER_WG.  Six values, in order:
+ *   v[0] grid_map       0 linear, 1 XCD-contiguous, 2 stripe groups per XCD
+ *   v[1] map_group      stripes per group, reduced to a power-of-two fraction of the option that divides S / 8
+ *   v[2] cols_per_wg    16-byte columns per workgroup
+ *   v[3] wg_per_stripe  workgroups per stripe and row tile
+ *   v[4] S              stripes of the launch
+ *   v[5] rtiles         row tiles (gridDim.y)
+ * All zero before the first such launch; byte-kernel launches (tails, unaligned blocks) do not change it.  Host
+ * only.  Returns the number of values, 6; v is written when cap >= 6 (v may be NULL with cap == 0). */
+int ecg_scrub_last_launch(int* v, int cap);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,10 @@ with k covering every load-batch branch and remainder, and a zero column in each
 
 INLINE (pointers in the kernel arguments) is reached through ecg_locate.ec, whose matrix is the handle's own:
 RS(k, r) gives [C | I] checks of r = 1..8 rows, PC(k1, 1, k2, 1) general ones of r = 3..8.
+
+Wide checks (n = 62..65, 126..128; tests/check_geometry_cases.py wide_plan) damage every block, so that the counters of
+all three registers, every word of the packed pivots and the whole ratio program are compared with the definition.
+The launch geometries (workgroup -> chunk maps, column-loop lengths) are tests/test_gpu_check_geometry.py's.
 """
 import json
 import os
@@ -23,6 +27,7 @@ import os
 import numpy as np
 import pytest
 
+import check_geometry_cases as G
 import gf_kernel_cases as C
 import gf_plain
 import locate_plain as LP
@@ -390,6 +395,118 @@ def test_larger_codes_are_refused(ecg, torch_cuda, locate, name):
         locate.ec(code, [d[0, j] for j in range(code.k)], [d[0, code.k + j] for j in range(code.m)], 64)
     assert e.value.code == ecg.ECG_EINVAL
     assert locate.counters()["launches"] == l0
+
+
+# ---- wide checks: n + 2 counters in three registers per lane (counter 64 j + i in lane i of register j), pivot rows
+# eight per word, r x n ratio tables, 128 pointers in the kernel arguments.  Plans: check_geometry_cases.wide_plan,
+# checked against the definition by tests/test_check_geometry_cases.py.
+
+def _wide_reference(n, r):
+    """(C, stripes [3][n][B_MAIN], votes [3][n + 2] by the definition) of a wide case, worked out once."""
+    def make():
+        Cm, stripes = G.wide_stripes(gf_plain.apply, n, r)
+        H = np.concatenate([Cm, np.eye(r, dtype=np.int64)], axis=1)
+        return Cm, stripes, np.stack([LP.votes(H, stripes[s]) for s in range(3)])
+    return G.memo(("wide", n, r), make)
+
+
+def _wide_strided(torch, locate, n, r, shift=0):
+    """H = [C | I] over n blocks, then the same check with its columns reversed (a general H: all n columns through
+    the tables, pivots and ratios in the opposite words)."""
+    Cm, stripes, votes = _wide_reference(n, r)
+    B = B_MAIN
+    img = _arena(np.concatenate([np.full((S3, 1, B), 0x77, np.uint8), stripes], axis=1))   # slot 0 is not named
+    d = _to_dev(torch, img, shift)
+    view = d[:, :, GUARD:GUARD + B]
+    H = np.concatenate([Cm, np.eye(r, dtype=np.int64)], axis=1)
+    src = list(range(1, n + 1))
+    g = _check_call(torch, locate, img, d, B, shift, H, src, lambda: locate.matrix_batch(H, src, view),
+                    memo={s: votes[s] for s in range(S3)})
+    assert not g[0].any() and g[1, n] > 0 and g[2, n] > g[1, n]
+    Hr, srcr = H[:, ::-1].copy(), src[::-1]
+    _check_call(torch, locate, img, d, B, shift, Hr, srcr, lambda: locate.matrix_batch(Hr, srcr, view),
+                memo={s: np.concatenate([votes[s][n - 1::-1], votes[s][n:]]) for s in range(S3)})
+
+
+@gpu
+@pytest.mark.parametrize("n,r", G.WIDE_CASES, ids=[f"n{n}-r{r}" for n, r in G.WIDE_CASES])
+def test_wide_checks_strided(torch_cuda, locate, n, r):
+    _wide_strided(torch_cuda, locate, n, r)
+
+
+@gpu
+def test_wide_check_through_the_byte_kernel(torch_cuda, locate):
+    """n = 128, r = 8 with the arena shifted by one byte: tally<8, 1> credits all three registers."""
+    _wide_strided(torch_cuda, locate, 128, 8, shift=1)
+
+
+@gpu
+@pytest.mark.parametrize("k,m", G.WIDE_INLINE, ids=[f"RS({k},{m})" for k, m in G.WIDE_INLINE])
+def test_wide_checks_inline(ecg, torch_cuda, locate, k, m):
+    """ecg_locate.ec over k + m = 128 (and 64) block pointers in the kernel arguments, the handle's own check."""
+    torch = torch_cuda
+    code = ecg.ec_factory(ecg.ECTYPE.RS, ecg.CodingParameters(k=k, m=m))
+    n, B = k + m, B_MAIN
+    H = np.asarray(code.check_matrix(), dtype=np.int64)
+    assert H.shape == (m, n) and np.array_equal(H[:, k:], np.eye(m, dtype=np.int64))
+    stripes = G.consistent(gf_plain.apply, H[:, :k], S3, B, 300 + n)
+    G.apply_plan(stripes, G.wide_plan(n, m, seed=1))
+    for s in range(S3):
+        img = _arena(np.concatenate([np.full((1, 1, B), 0x77, np.uint8), stripes[s:s + 1]], axis=1))
+        d = _to_dev(torch, img)
+        blocks = [d[0, 1 + b, GUARD:GUARD + B] for b in range(n)]
+        g = _check_call(torch, locate, img, d, B, 0, H, list(range(1, n + 1)),
+                        lambda: locate.ec(code, blocks[:k], blocks[k:], B))
+        if s:
+            assert (g[0, :n] > 0).all() and g[0, n] >= sum(G.block_count(b) for b in range(n))
+        else:
+            assert not g.any()
+
+
+@gpu
+def test_n_129_is_refused(ecg, torch_cuda, locate):
+    """RS(121, 8) has n = 129 > 128: ECG_EINVAL from both forms, nothing launched."""
+    torch = torch_cuda
+    k, m = G.WIDE_REFUSED
+    code = ecg.ec_factory(ecg.ECTYPE.RS, ecg.CodingParameters(k=k, m=m))
+    d = torch.zeros((2, k + m, 64), dtype=torch.uint8, device="cuda")
+    l0 = locate.counters()["launches"]
+    with pytest.raises(ecg.EcgError) as e:
+        locate.ec(code, [d[0, j] for j in range(k)], [d[0, k + j] for j in range(m)], 64)
+    assert e.value.code == ecg.ECG_EINVAL and b"n = 129" in ecg.lib().ecg_last_error()
+    with pytest.raises(ecg.EcgError) as e:
+        locate.ec_batch(code, d)
+    assert e.value.code == ecg.ECG_EINVAL
+    assert locate.counters()["launches"] == l0
+
+
+# ---- an all-zero matrix row: encode_check leaves its H row and its parity column zero
+
+@gpu
+def test_all_zero_matrix_row(torch_cuda, locate):
+    """encode_batch with row 1 of the RS(6,4) matrix zeroed: parity block k + 1 is checked by no row, so it is no
+    candidate and damage in it is invisible; everything else is located as by the definition over that H."""
+    torch = torch_cuda
+    k, m, B = 6, 4, B_MAIN
+    n = k + m
+    M = np.asarray(RS64["matrix"], dtype=np.int64).reshape(m, k).copy()
+    M[1] = 0
+    stripes = _consistent(M, S3, B, 68)
+    assert not stripes[:, k + 1].any()
+    H = np.concatenate([M, np.eye(m, dtype=np.int64)], axis=1)
+    H[1, k + 1] = 0
+    for i, p in enumerate(POSITIONS):
+        stripes[1, k + 1, p] ^= 0x10 + i                            # stripe 1: the unchecked block only
+        stripes[2, (0, n // 2, n - 1)[i % 3], p] ^= 0x21 + i        # stripe 2: a data block, two checked parities
+    stripes[2, k + 1, 100:140] ^= 0x5A                              # and the unchecked one
+    img = _arena(stripes)
+    d = _to_dev(torch, img)
+    view = d[:, :, GUARD:GUARD + B]
+    flat = [int(v) for v in M.reshape(-1)]
+    g = _check_call(torch, locate, img, d, B, 0, H, list(range(n)), lambda: locate.encode_batch(k, m, flat, view))
+    assert not g[0].any() and not g[1].any()
+    assert g[2, n] == len(POSITIONS) and g[2, n + 1] == 0 and not g[:, k + 1].any()
+    assert [int(v) for v in g[2, [0, n // 2, n - 1]]] == [3, 2, 2]
 
 
 # ---- scrub -> dirty -> locate -> verdict -> decode -> re-scrub

@@ -14,6 +14,9 @@ INLINE (pointers in the kernel arguments) is reached through ecg_scrub.ec, whose
 gives GENERAL [C | I] tiles of r = 2..8 rows (one-row Vandermonde codes are all ones, so GENERAL MT = 1 has no INLINE
 call), RS(k, 1) and HVPC(k1, 1, k2, 1) the BINARY ones; product codes, whose column checks read row parities, give
 general checks: BINARY PC(k1, 1, k2, 1) from 3 rows, GENERAL PC(k1, 2, 1, 1) from 6.
+
+Wide checks run k = 33 and k = 128 table columns, STRIDED on the widest tiles and INLINE on RS(120, 8).  The launch
+geometries (workgroup -> chunk maps, column-loop lengths) are tests/test_gpu_check_geometry.py's.
 """
 import ctypes
 import json
@@ -22,6 +25,7 @@ import os
 import numpy as np
 import pytest
 
+import check_geometry_cases as G
 import gf_kernel_cases as C
 import gf_plain
 
@@ -262,6 +266,76 @@ def test_counts_are_overwritten_not_accumulated(torch_cuda, scrub):
     for _ in range(2):
         scrub.encode_batch(k, m, flat, d, out=out)
         assert np.array_equal(out.cpu().numpy(), want)
+
+
+# ---- wide checks: as many table columns as an INLINE launch has pointers (kInlineSrc = 128), and one past a batch
+
+WIDE_K = (33, 128)
+
+
+@gpu
+@pytest.mark.parametrize("k", WIDE_K, ids=[f"k{k}" for k in WIDE_K])
+def test_wide_checks_strided(torch_cuda, scrub, k):
+    """k columns through the tables (a general H) and [C | I] with k + r <= 128 blocks, on the widest GENERAL and
+    BINARY tiles."""
+    for binary, r in ((0, 8), (1, 16)):
+        _strided_case(torch_cuda, scrub, binary, r, k, C.B_MAIN)
+        _encode_shaped_case(torch_cuda, scrub, binary, r, min(k, 128 - r), C.B_MAIN)
+
+
+@gpu
+def test_wide_check_inline(ecg, torch_cuda, scrub):
+    """ecg_scrub.ec on RS(120, 8): 128 block pointers in the kernel arguments."""
+    torch = torch_cuda
+    code = ecg.ec_factory(ecg.ECTYPE.RS, ecg.CodingParameters(k=120, m=8))
+    k, m, B = code.k, code.m, C.B_MAIN
+    H = np.asarray(code.check_matrix(), dtype=np.int64)
+    assert H.shape == (8, 128)
+    img = _arena(np.random.default_rng(120), 1, k + m + 1, B)
+    d = _to_dev(torch, img)
+    blocks = [d[0, 1 + b, GUARD:GUARD + B] for b in range(k + m)]
+    _check_call(torch, scrub, img, d, B, 0, H, list(range(1, k + m + 1)),
+                lambda: scrub.ec(code, blocks[:k], blocks[k:], B), strided=False, ident=True)
+    # a stripe that satisfies the check, damaged by the wide locate plan: sparse counts, every block's column
+    stripes = G.consistent(gf_plain.apply, H[:, :k], 1, B, 428)
+    G.apply_plan(stripes, [(0, b, pos, val) for s, b, pos, val in G.wide_plan(k + m, m) if s == 2])
+    img = _arena(None, 1, k + m + 1, B, blocks=np.concatenate([np.zeros((1, 1, B), np.uint8), stripes], axis=1))
+    d = _to_dev(torch, img)
+    blocks = [d[0, 1 + b, GUARD:GUARD + B] for b in range(k + m)]
+    want = _check_call(torch, scrub, img, d, B, 0, H, list(range(1, k + m + 1)),
+                       lambda: scrub.ec(code, blocks[:k], blocks[k:], B), strided=False, ident=True)
+    assert (want > 0).all() and (want < 500).all()
+
+
+# ---- an all-zero matrix row: encode_check leaves its H row and its parity column zero
+
+@gpu
+def test_all_zero_matrix_row(torch_cuda, scrub):
+    """encode_batch with row 1 of the RS(6,4) matrix zeroed: row 1 checks nothing, so its count stays zero and damage
+    in parity block k + 1 is invisible; damage elsewhere is counted as by the definition over that H."""
+    torch = torch_cuda
+    k, m, B = 6, 4, C.B_MAIN
+    M = np.asarray(RS64["matrix"], dtype=np.int64).reshape(m, k).copy()
+    M[1] = 0
+    rng = np.random.default_rng(69)
+    stripes = np.zeros((S3, k + m, B), np.uint8)
+    for s in range(S3):
+        stripes[s, :k] = rng.integers(0, 256, (k, B), dtype=np.uint8)
+        stripes[s, k:] = gf_plain.apply(M, stripes[s, :k])
+    assert not stripes[:, k + 1].any()
+    H = np.concatenate([M, np.eye(m, dtype=np.int64)], axis=1)
+    H[1, k + 1] = 0
+    for i, p in enumerate(POSITIONS):
+        stripes[1, k + 1, p] ^= 0x10 + i                            # stripe 1: the unchecked block only
+        stripes[2, (0, 5, k + m - 1)[i % 3], p] ^= 0x21 + i         # stripe 2: data blocks and a checked parity
+    stripes[2, k + 1, 100:140] ^= 0x5A                              # and the unchecked one
+    img = _arena(None, S3, k + m, B, blocks=stripes)
+    d = _to_dev(torch, img)
+    flat = [int(v) for v in M.reshape(-1)]
+    want = _check_call(torch, scrub, img, d, B, 0, H, list(range(k + m)),
+                       lambda: scrub.encode_batch(k, m, flat, _blocks(d, B)), ident=False)
+    assert not want[0].any() and not want[1].any() and not want[:, 1].any()
+    assert [int(v) for v in want[2]] == [6, 0, 6, 8]               # 3 + 3 data bytes; parity 9 adds 2 to its own row
 
 
 # ---- the ErasureCode facade

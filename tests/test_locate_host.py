@@ -51,10 +51,26 @@ def _stripe(c, seed=1):
 
 # ---- the library
 
+def test_last_launch_reports_six_fields(locate):
+    """The field count without a buffer; a buffer that is too small stays untouched; the binding names the fields in
+    the header's order."""
+    L = locate.lib()
+    assert L.ecg_locate_last_launch(None, 0) == 6
+    small = (ctypes.c_int * 5)(*([77] * 5))
+    assert L.ecg_locate_last_launch(small, 5) == 6 and list(small) == [77] * 5
+    full = (ctypes.c_int * 8)(*([77] * 8))
+    assert L.ecg_locate_last_launch(full, 8) == 6 and list(full)[6:] == [77, 77]
+    got = locate.last_launch()
+    assert list(got) == ["grid_map", "map_group", "cols_per_wg", "wg_per_stripe", "S", "rtiles"]
+    assert list(got.values()) == list(full)[:6] and all(v >= 0 for v in got.values())
+    hdr = open(os.path.join(ROOT, "include", "ecg_locate.h")).read()
+    assert re.findall(r"v\[(\d)\] (\w+)", hdr) == [(str(i), name) for i, name in enumerate(got)]
+
+
 def test_header_symbols_exported(locate):
     hdr = open(os.path.join(ROOT, "include", "ecg_locate.h")).read()
     declared = sorted(set(re.findall(r"\b(ecg_locate_\w+)\s*\(", hdr)))
-    assert len(declared) == 6
+    assert len(declared) == 7
     assert sorted(locate.EXPORTS) == declared
     out = subprocess.run(["nm", "-D", "--defined-only", locate.LIB_PATH], capture_output=True, text=True).stdout
     exported = sorted(set(re.findall(r" T (ecg_\w+)", out)))

@@ -31,10 +31,26 @@ def scrub(ecg):
 
 # ---- the library
 
+def test_last_launch_reports_six_fields(scrub):
+    """The field count without a buffer; a buffer that is too small stays untouched; the binding names the fields in
+    the header's order."""
+    L = scrub.lib()
+    assert L.ecg_scrub_last_launch(None, 0) == 6
+    small = (ctypes.c_int * 5)(*([77] * 5))
+    assert L.ecg_scrub_last_launch(small, 5) == 6 and list(small) == [77] * 5
+    full = (ctypes.c_int * 8)(*([77] * 8))
+    assert L.ecg_scrub_last_launch(full, 8) == 6 and list(full)[6:] == [77, 77]
+    got = scrub.last_launch()
+    assert list(got) == ["grid_map", "map_group", "cols_per_wg", "wg_per_stripe", "S", "rtiles"]
+    assert list(got.values()) == list(full)[:6] and all(v >= 0 for v in got.values())
+    hdr = open(os.path.join(ROOT, "include", "ecg_scrub.h")).read()
+    assert re.findall(r"v\[(\d)\] (\w+)", hdr) == [(str(i), name) for i, name in enumerate(got)]
+
+
 def test_header_symbols_exported(scrub):
     hdr = open(os.path.join(ROOT, "include", "ecg_scrub.h")).read()
     declared = sorted(set(re.findall(r"\b(ecg_scrub_\w+)\s*\(", hdr)))
-    assert len(declared) == 6
+    assert len(declared) == 7
     assert sorted(scrub.EXPORTS) == declared
     out = subprocess.run(["nm", "-D", "--defined-only", scrub.LIB_PATH], capture_output=True, text=True).stdout
     exported = set(re.findall(r" T (ecg_\w+)", out))
