@@ -1,5 +1,5 @@
-// Host-side pieces shared by the entry points over a check matrix H: scrub.cpp (libecg_scrub.so) and locate.cpp
-// (libecg_locate.so).  Header-only; no HIP launch and no state.
+// Host-side pieces shared by the entry points over a check matrix H: scrub.cpp (libecg_scrub.so), locate.cpp
+// (libecg_locate.so) and heal.cpp (libecg_heal.so).  Header-only; no HIP launch and no state.
 #pragma once
 #include <stdint.h>
 

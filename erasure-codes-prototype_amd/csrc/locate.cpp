@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/ecg_locate.h"
+#include "candidate_plan.hpp"
 #include "capi_handle.hpp"
 #include "check_common.hpp"
 #include "engine.hpp"
@@ -19,32 +20,7 @@ using namespace ecg;
 
 namespace {
 
-struct Plan {
-    Check chk;
-    LinearOp ratio;  // r x n: H[q][b] / H[p0(b)][b]; an all-zero column for a zero column of H
-    unsigned p0[kInlineSrc / 8];
-    int n = 0, r = 0;
-};
-
-Plan make_plan(int n, int r, const int* H, const int* src_ids, bool consecutive) {
-    Plan pl;
-    pl.n = n;
-    pl.r = r;
-    pl.chk = make_check(n, r, H, src_ids, consecutive);
-    pl.ratio.src_ids = iota(n);
-    pl.ratio.dst_ids = iota(r);
-    pl.ratio.coef.assign((size_t)r * n, 0);
-    memset(pl.p0, 0, sizeof(pl.p0));
-    for (int b = 0; b < n; b++) {
-        int p0 = 0;
-        while (p0 < r && (H[(size_t)p0 * n + b] & 0xff) == 0) p0++;
-        pl.p0[b >> 3] |= (p0 < r ? (unsigned)p0 : kNoPivot) << ((b & 7) * 4);
-        if (p0 == r) continue;
-        const int lead = H[(size_t)p0 * n + b] & 0xff;
-        for (int q = p0; q < r; q++) pl.ratio.coef[(size_t)q * n + b] = (uint8_t)gf::div(H[(size_t)q * n + b], lead);
-    }
-    return pl;
-}
+using Plan = CandidatePlan;  // candidate_plan.hpp: make_plan, shared with heal.cpp
 
 int too_large(long long n, int r) {
     set_last_error("locate: r = " + std::to_string(r) + ", n = " + std::to_string(n) + " exceeds r <= " +
