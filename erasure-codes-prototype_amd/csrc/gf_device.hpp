@@ -1,6 +1,8 @@
 // Device-side building blocks shared by the GF(2^8) kernel families: the region product (gf_kernels.hip, in
-// libecg.so) and the read-only parity check (scrub_kernels.hip, in libecg_scrub.so).  Everything here is
-// inlined into the kernels that use it; the header defines no kernel and no host state.
+// libecg.so) and, through check_device.hpp, the kernels over a check matrix -- the scrub (scrub_kernels.hip, in
+// libecg_scrub.so), the locate (locate_kernels.hip, in libecg_locate.so) and the heal (heal_kernels.hip, in
+// libecg_heal.so).  Everything here is inlined into the kernels that use it; the header defines no kernel and no
+// host state.
 #pragma once
 #include "gf_kernels.hpp"
 

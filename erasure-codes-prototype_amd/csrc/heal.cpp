@@ -59,12 +59,7 @@ bool columns_distinct(const CandidatePlan& pl, int& a_out, int& b_out) {
     return true;
 }
 
-int too_large(long long n, int r) {
-    set_last_error("heal: r = " + std::to_string(r) + ", n = " + std::to_string(n) + " exceeds r <= " +
-                   std::to_string(kMaxMT) + ", n <= " + std::to_string(kInlineSrc) +
-                   " (one lane holds all r syndromes); product codes stay with ecg_scrub_suspects and a decode");
-    return ECG_EINVAL;
-}
+constexpr TooLarge too_large{"heal", " and a decode"};
 
 // ANY mode corrects every block that explains a position: refused unless at most one can.
 int check_any(const CandidatePlan& pl) {
@@ -76,57 +71,31 @@ int check_any(const CandidatePlan& pl) {
     return ECG_EINVAL;
 }
 
-// Flush the thread's batch scope, fetch the table sets, zero the report, launch.  `fill` sets the launch's sources.
+// The locate's launch descriptor with the report zeroed (candidate_plan.hpp prepare_launch), the pivot inverses' tables
+// and the candidate set on top of it, then the launch.  `fill` sets the launch's sources.
 template <class Fill>
 int run_heal(const HealPlan& hp, int mode, long long B, int S, const int* d_stripe_ids, const int* d_targets,
              int target, bool any, unsigned* d_report, bool vec_ok, hipStream_t st, Fill fill) {
-    const CandidatePlan& pl = hp.cand;
-    if (const int rc = batch_flush_pending(); rc != ECG_OK) return rc;
-    Engine& eng = Engine::instance();
-    int status = ECG_OK;
-    std::shared_ptr<ProgramSet> ps = eng.program_set(&pl.chk.op, 1, &status, st);
-    if (!ps) return status;
-    std::shared_ptr<ProgramSet> rs = eng.program_set(&pl.ratio, 1, &status, st);
-    if (!rs) return status;
-    std::shared_ptr<ProgramSet> is = eng.program_set(&hp.inv, 1, &status, st);
-    if (!is) return status;
-    if (const int rc = ps->ensure_ready(st); rc != ECG_OK) return rc;
-    if (const int rc = rs->ensure_ready(st); rc != ECG_OK) return rc;
-    if (const int rc = is->ensure_ready(st); rc != ECG_OK) return rc;
-    if (ps->MT != pl.r || ps->rtiles != 1 || rs->MT != pl.r || rs->rtiles != 1 || rs->k != pl.n || is->MT != 1 ||
-        is->rtiles != 1 || is->k != pl.n)
-        return ECG_EINVAL;
     HealLaunch h;
     memset(&h, 0, sizeof(h));
-    LocateLaunch& a = h.l;
-    a.g.tabs = ps->d_tabs;
-    a.g.src_ids = ps->d_src;
-    a.g.dst_ids = ps->d_dst;
-    a.g.stripe_of = d_stripe_ids;
-    a.g.B = B;
-    a.g.k = ps->k;
-    a.g.m = ps->m;
-    a.g.S = S;
-    a.g.MT = ps->MT;
-    a.g.rtiles = ps->rtiles;
-    a.g.binary = 0;  // the GENERAL flavour always: the tables of 0 and 1 are exact
-    a.votes = d_report;
-    a.ident = pl.chk.ident;
-    a.ident_base = pl.chk.ident_base;
-    a.ratios = rs->d_tabs;
-    a.n = pl.n;
-    memcpy(a.p0, pl.p0, sizeof(a.p0));
+    CandidateTables t;
+    if (const int rc =
+            prepare_launch(hp.cand, B, S, d_stripe_ids, d_report, "hipMemsetAsync(heal report)", st, fill, h.l, t);
+        rc != ECG_OK)
+        return rc;
+    Engine& eng = Engine::instance();
+    int status = ECG_OK;
+    std::shared_ptr<ProgramSet> is = eng.program_set(&hp.inv, 1, &status, st);
+    if (!is) return status;
+    if (const int rc = is->ensure_ready(st); rc != ECG_OK) return rc;
+    if (is->MT != 1 || is->rtiles != 1 || is->k != hp.cand.n) return ECG_EINVAL;
     h.invlead = is->d_tabs;
     h.targets = d_targets;
     h.target = target;
     h.any = any ? 1 : 0;
-    fill(a.g);
-    if (const hipError_t e = hipMemsetAsync(d_report, 0, (size_t)S * (size_t)(pl.n + 2) * sizeof(unsigned), st);
-        e != hipSuccess)
-        return hip_fail(e, "hipMemsetAsync(heal report)");
     if (const hipError_t e = launch_heal(h, mode, vec_ok, st); e != hipSuccess) return hip_fail(e, "launch_heal");
-    eng.note_launch(*ps, st);
-    eng.note_launch(*rs, st);
+    eng.note_launch(*t.chk, st);
+    eng.note_launch(*t.ratio, st);
     eng.note_launch(*is, st);
     return ECG_OK;
 }
@@ -175,11 +144,8 @@ int ecg_heal_ec_batch(ecg_ec* ec, void* d_stripes, long long sstride, long long 
                       const int* d_stripe_ids, const int* d_targets, int S_sel, unsigned* d_report, void* stream) {
     if (!ec || bad_sizes(B, S_sel) || !d_stripes || !d_report || ec->impl->mem != ECG_MEM_DEVICE) return ECG_EINVAL;
     std::vector<int> H;
-    const int r = ec->impl->check_matrix(H);
-    if (r < 0) return r;
-    if (r < 1) return ECG_EINVAL;
-    const int n = (int)(H.size() / (size_t)r);
-    if (r > kMaxMT || n > kInlineSrc) return too_large(n, r);
+    int n, r;
+    if (const int rc = ec_check(ec, too_large, H, n, r); rc != ECG_OK) return rc;
     const std::vector<int> ids = iota(n);
     return run_strided_heal(n, r, H.data(), ids.data(), d_stripes, sstride, bstride, B, d_stripe_ids, d_targets, S_sel,
                             d_report, (hipStream_t)stream);
@@ -190,11 +156,9 @@ int ecg_heal_ec(ecg_ec* ec, char** d_data_ptrs, char** d_coding_ptrs, int block_
     if (!ec || block_size < 0 || !d_data_ptrs || !d_coding_ptrs || !d_report || ec->impl->mem != ECG_MEM_DEVICE)
         return ECG_EINVAL;
     std::vector<int> H;
-    const int r = ec->impl->check_matrix(H);
-    if (r < 0) return r;
-    if (r < 1) return ECG_EINVAL;
-    const int k = ec->impl->k, n = (int)(H.size() / (size_t)r);
-    if (r > kMaxMT || n > kInlineSrc) return too_large(n, r);
+    int n, r;
+    if (const int rc = ec_check(ec, too_large, H, n, r); rc != ECG_OK) return rc;
+    const int k = ec->impl->k;
     if (target < -1 || target >= n) return ECG_EINVAL;
     for (int b = 0; b < n; b++)
         if (!(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k])) return ECG_EINVAL;

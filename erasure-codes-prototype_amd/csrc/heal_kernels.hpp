@@ -34,7 +34,6 @@ hipError_t launch_heal(const HealLaunch& base, int mode, bool vec_ok, hipStream_
 // written depend on the data and are not counted).
 void heal_traffic(long long* launches, long long* bytes);
 // Geometry of this process's most recent vector-path launch: the six fields of locate_last_launch.
-constexpr int kHealLaunchFields = kLocateLaunchFields;
 int heal_last_launch(int* v, int cap);
 
 }  // namespace ecg

@@ -22,53 +22,21 @@ namespace {
 
 using Plan = CandidatePlan;  // candidate_plan.hpp: make_plan, shared with heal.cpp
 
-int too_large(long long n, int r) {
-    set_last_error("locate: r = " + std::to_string(r) + ", n = " + std::to_string(n) + " exceeds r <= " +
-                   std::to_string(kMaxMT) + ", n <= " + std::to_string(kInlineSrc) +
-                   " (one lane holds all r syndromes); product codes stay with ecg_scrub_suspects");
-    return ECG_EINVAL;
-}
+constexpr TooLarge too_large{"locate", ""};
 
-// Flush the thread's batch scope, fetch both table sets, zero the votes, launch.  `fill` sets the launch's sources.
+// The launch descriptor with the votes zeroed (candidate_plan.hpp prepare_launch), then the launch.  `fill` sets the
+// launch's sources.
 template <class Fill>
 int run_locate(const Plan& pl, int mode, long long B, int S, const int* d_stripe_ids, unsigned* d_votes, bool vec_ok,
                hipStream_t st, Fill fill) {
-    if (const int rc = batch_flush_pending(); rc != ECG_OK) return rc;
-    Engine& eng = Engine::instance();
-    int status = ECG_OK;
-    std::shared_ptr<ProgramSet> ps = eng.program_set(&pl.chk.op, 1, &status, st);
-    if (!ps) return status;
-    std::shared_ptr<ProgramSet> rs = eng.program_set(&pl.ratio, 1, &status, st);
-    if (!rs) return status;
-    if (const int rc = ps->ensure_ready(st); rc != ECG_OK) return rc;
-    if (const int rc = rs->ensure_ready(st); rc != ECG_OK) return rc;
-    if (ps->MT != pl.r || ps->rtiles != 1 || rs->MT != pl.r || rs->rtiles != 1 || rs->k != pl.n) return ECG_EINVAL;
     LocateLaunch a;
-    memset(&a, 0, sizeof(a));
-    a.g.tabs = ps->d_tabs;
-    a.g.src_ids = ps->d_src;
-    a.g.dst_ids = ps->d_dst;
-    a.g.stripe_of = d_stripe_ids;
-    a.g.B = B;
-    a.g.k = ps->k;
-    a.g.m = ps->m;
-    a.g.S = S;
-    a.g.MT = ps->MT;
-    a.g.rtiles = ps->rtiles;
-    a.g.binary = 0;  // the GENERAL flavour always: the tables of 0 and 1 are exact
-    a.votes = d_votes;
-    a.ident = pl.chk.ident;
-    a.ident_base = pl.chk.ident_base;
-    a.ratios = rs->d_tabs;
-    a.n = pl.n;
-    memcpy(a.p0, pl.p0, sizeof(a.p0));
-    fill(a.g);
-    if (const hipError_t e = hipMemsetAsync(d_votes, 0, (size_t)S * (size_t)(pl.n + 2) * sizeof(unsigned), st);
-        e != hipSuccess)
-        return hip_fail(e, "hipMemsetAsync(locate votes)");
+    CandidateTables t;
+    if (const int rc = prepare_launch(pl, B, S, d_stripe_ids, d_votes, "hipMemsetAsync(locate votes)", st, fill, a, t);
+        rc != ECG_OK)
+        return rc;
     if (const hipError_t e = launch_locate(a, mode, vec_ok, st); e != hipSuccess) return hip_fail(e, "launch_locate");
-    eng.note_launch(*ps, st);
-    eng.note_launch(*rs, st);
+    Engine::instance().note_launch(*t.chk, st);
+    Engine::instance().note_launch(*t.ratio, st);
     return ECG_OK;
 }
 
@@ -111,11 +79,8 @@ int ecg_locate_ec_batch(ecg_ec* ec, const void* d_stripes, long long sstride, lo
                         const int* d_stripe_ids, int S_sel, unsigned* d_votes, void* stream) {
     if (!ec || bad_sizes(B, S_sel) || !d_stripes || !d_votes || ec->impl->mem != ECG_MEM_DEVICE) return ECG_EINVAL;
     std::vector<int> H;
-    const int r = ec->impl->check_matrix(H);
-    if (r < 0) return r;
-    if (r < 1) return ECG_EINVAL;
-    const int n = (int)(H.size() / (size_t)r);
-    if (r > kMaxMT || n > kInlineSrc) return too_large(n, r);
+    int n, r;
+    if (const int rc = ec_check(ec, too_large, H, n, r); rc != ECG_OK) return rc;
     if (S_sel == 0 || B == 0) return ECG_OK;
     const std::vector<int> ids = iota(n);
     return run_strided_locate(make_plan(n, r, H.data(), ids.data(), true), d_stripes, sstride, bstride, B,
@@ -126,11 +91,9 @@ int ecg_locate_ec(ecg_ec* ec, char** d_data_ptrs, char** d_coding_ptrs, int bloc
     if (!ec || block_size < 0 || !d_data_ptrs || !d_coding_ptrs || !d_votes || ec->impl->mem != ECG_MEM_DEVICE)
         return ECG_EINVAL;
     std::vector<int> H;
-    const int r = ec->impl->check_matrix(H);
-    if (r < 0) return r;
-    if (r < 1) return ECG_EINVAL;
-    const int k = ec->impl->k, n = (int)(H.size() / (size_t)r);
-    if (r > kMaxMT || n > kInlineSrc) return too_large(n, r);
+    int n, r;
+    if (const int rc = ec_check(ec, too_large, H, n, r); rc != ECG_OK) return rc;
+    const int k = ec->impl->k;
     for (int b = 0; b < n; b++)
         if (!(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k])) return ECG_EINVAL;
     if (block_size == 0) return ECG_OK;

@@ -5,25 +5,25 @@
 //   votes[b] = #{ x : s[x] = e * H[:, b], e != 0 },  votes[n] = #{ x : s[x] != 0 },  votes[n + 1] = #{ bad x that no
 //   single block explains }.
 //
-// The data path is the scrub's (scrub_kernels.hip; shared pieces in gf_device.hpp): one lane per 16-byte column,
-// non-temporal dwordx4 loads, CoefTab tables in SGPRs, the same folds and load batches, the same workgroup -> chunk
-// maps, and for H = [C | I] only C through the tables with the stored blocks XORed in.  The difference:
-// ONE lane holds all R <= 8 syndromes of its column (one row tile, GENERAL flavour; c = 0 and c = 1 tables are exact,
-// so a 0/1 H runs through it too).  A wave whose syndromes are all zero goes on to its next column after one
-// OR-reduce per lane and one ballot: clean data costs what the scrub costs.  Any other wave runs the candidate test:
-// a uniform loop over the blocks b, with p0 = p0(b) the first row where column b is nonzero,
+// The data path is the scrub's (scrub_kernels.hip; shared pieces in gf_device.hpp and check_device.hpp): one lane per
+// 16-byte column, non-temporal dwordx4 loads, CoefTab tables in SGPRs, the same folds and load batches, the same
+// workgroup -> chunk maps, and for H = [C | I] only C through the tables with the stored blocks XORed in.  The
+// difference: ONE lane holds all R <= 8 syndromes of its column (one row tile, GENERAL flavour; c = 0 and c = 1 tables
+// are exact, so a 0/1 H runs through it too).  A wave whose syndromes are all zero goes on to its next column after one
+// OR-reduce per lane and one ballot: clean data costs what the scrub costs.  Any other wave runs the candidate test
+// (check_device.hpp candidate_loop, which the heal shares): a uniform loop over the blocks b, with p0 = p0(b) the
+// first row where column b is nonzero,
 //   residual = OR_q  s_q ^ (H[q][b] / H[p0][b]) * s_p0          (ratio tables; the term q = p0 is s_p0 ^ 1 * s_p0 = 0:
 //                                                                 kept, so the loop needs no row index in a register)
 //   votes    = bytes where s_p0 != 0 and residual == 0
-// by the 0x7f7f7f7f / 0x80808080 byte masks of the scrub.  s_p0 is picked by R - 1 selects on the uniform p0, never
-// by indexing the accumulators (that would put them in scratch).  A candidate no lane votes for costs one ballot; the
-// others are summed over the wave at once and added to the lane that owns the counter (lane i of register j owns
-// counter 64 j + i), so the n + 2 counters of a wave live in three VGPRs, statically indexed, and leave it in at
-// most three atomic instructions -- none when they are all zero: a clean stripe writes nothing.  No LDS, no barrier.
+// by the 0x7f / 0x80 byte masks of the scrub.  s_p0 is picked by R - 1 selects on the uniform p0, never by indexing
+// the accumulators (that would put them in scratch).  A candidate no lane votes for costs one ballot; the others are
+// summed over the wave at once and added to the lane that owns the counter (lane i of register j owns counter
+// 64 j + i), so the n + 2 counters of a wave live in three VGPRs, statically indexed, and leave it in at most three
+// atomic instructions -- none when they are all zero: a clean stripe writes nothing.  No LDS, no barrier.
 // Integer adds commute: the counts are exact and reproducible.
-#include <atomic>
-
-#include "gf_device.hpp"
+#include "check_device.hpp"
+#include "check_launch.hpp"
 #include "locate_kernels.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -34,114 +34,11 @@ namespace ecg {
 
 namespace {
 
-static_assert(kThreads % 64 == 0, "whole waves");
-static_assert(kInlineSrc + 2 <= 3 * 64, "three counter registers per lane hold n + 2 counters");
-constexpr int kSlots = 3;
-
-// One bit (bit 7) per nonzero byte of a dword: adding 0x7f to the low 7 bits of a byte carries into its bit 7
-// exactly when they are not all zero (no carry leaves the byte), OR-ing x brings in bit 7 itself.
-__device__ __forceinline__ uint32_t nonzero_mask(uint32_t x) {
-    const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-    return (t | x) & 0x80808080u;
-}
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// counter idx += tot, in the lane that owns it (idx and tot are uniform)
-__device__ __forceinline__ void credit(unsigned (&mine)[kSlots], int idx, unsigned tot, int lane) {
-    const unsigned add = lane == (idx & 63) ? tot : 0u;
-    const int slot = idx >> 6;
-#pragma unroll
-    for (int j = 0; j < kSlots; ++j) mine[j] += slot == j ? add : 0u;
-}
-
-// Block pointers.  STRIDED: `sbase` is the selected stripe's base, in_base + stripe_of[s] * in_sstride, worked out once
-// per workgroup (gf_device.hpp src_ptr tests stripe_of at every load); INLINE: the pointers in the kernel arguments.
-template <int MODE>
-__device__ __forceinline__ const uint8_t* stripe_base(const GfLaunch& a, int s) {
-    if constexpr (MODE == GF_MODE_INLINE) {
-        return nullptr;
-    } else {
-        const long long st = a.stripe_of ? (long long)cst(a.stripe_of)[s] : (long long)s;
-        return a.in_base + st * a.in_sstride;
-    }
-}
-
-// column j of the table part
-template <int MODE>
-__device__ __forceinline__ const uint8_t* col_ptr(const GfLaunch& a, const uint8_t* sbase, int j) {
-    if constexpr (MODE == GF_MODE_INLINE) return a.isrc[j];
-    else return sbase + (long long)cst(a.src_ids)[j] * a.in_bstride;
-}
-
-// the stored block of check row q of H = [C | I] (LocateLaunch::ident), folded in after the C part
-template <int MODE>
-__device__ __forceinline__ const uint8_t* ident_ptr(const LocateLaunch& sa, const uint8_t* sbase, int q) {
-    if constexpr (MODE == GF_MODE_INLINE) return sa.g.isrc[sa.g.k + q];
-    else return sbase + (long long)(sa.ident_base + q) * sa.g.in_bstride;
-}
-
-// The candidate test over the R syndromes of W dwords (W = 4: a 16-byte column; W = 1: one byte in a dword).  Every
-// lane of the wave is here (a lane past its chunk comes with zero syndromes): the wave sums read every lane.
+// The candidate test over every block: the votes are all a locate wants of it.
 template <int R, int W>
 __device__ __forceinline__ void tally(const LocateLaunch& sa, const uint32_t (&syn)[R][W], int lane,
                                       unsigned (&mine)[kSlots]) {
-    const ECG_CONST CoefTab* Q = cst(sa.ratios);
-    const int n = sa.n;
-    uint32_t bad[W], expl[W];
-#pragma unroll
-    for (int d = 0; d < W; ++d) {
-        uint32_t any = syn[0][d];
-#pragma unroll
-        for (int p = 1; p < R; ++p) any |= syn[p][d];
-        bad[d] = nonzero_mask(any);
-        expl[d] = 0u;
-    }
-    for (int b = 0; b < n; ++b) {  // uniform
-        const unsigned p0 = (sa.p0[b >> 3] >> ((b & 7) * 4)) & 15u;
-        if (p0 == kNoPivot) continue;  // a zero column explains nothing
-        const ECG_CONST CoefTab* t = Q + (size_t)b * R;
-        uint32_t vm[W];
-        unsigned v = 0u;
-#pragma unroll
-        for (int d = 0; d < W; ++d) {
-            uint32_t lead = syn[0][d];
-#pragma unroll
-            for (int p = 1; p < R; ++p) lead = p0 == (unsigned)p ? syn[p][d] : lead;
-            const Split sp = split(lead);
-            uint32_t res = 0u;
-#pragma unroll
-            for (int q = 0; q < R; ++q) res |= syn[q][d] ^ gmul(t[q], sp);
-            vm[d] = nonzero_mask(lead) & ~nonzero_mask(res);
-            v += (unsigned)__popc(vm[d]);
-        }
-        if (__ballot(v != 0u) == 0ull) continue;
-#pragma unroll
-        for (int d = 0; d < W; ++d) expl[d] |= vm[d];
-        credit(mine, b, wave_sum(v), lane);
-    }
-    unsigned nb = 0u, nu = 0u;
-#pragma unroll
-    for (int d = 0; d < W; ++d) {
-        nb += (unsigned)__popc(bad[d]);
-        nu += (unsigned)__popc(bad[d] & ~expl[d]);
-    }
-    credit(mine, n, wave_sum(nb), lane);
-    if (__ballot(nu != 0u) != 0ull) credit(mine, n + 1, wave_sum(nu), lane);
-}
-
-// A wave's counters -> votes[0, n + 2): one atomic instruction per register that holds a nonzero counter.
-__device__ __forceinline__ void post_votes(const unsigned (&mine)[kSlots], unsigned* out, int ncount, int lane) {
-    if (__ballot((mine[0] | mine[1] | mine[2]) != 0u) == 0ull) return;
-#pragma unroll
-    for (int j = 0; j < kSlots; ++j) {
-        const int idx = j * 64 + lane;
-        if (idx < ncount && mine[j] != 0u) atomicAdd(out + idx, mine[j]);
-    }
+    candidate_loop<R, W>(sa, syn, 0, sa.n, lane, mine, [](int, const uint32_t (&)[W], const uint32_t (&)[W]) {});
 }
 
 // Vector path: bytes [0, 16 * floor(B / 16)) of every block; all pointers 16-byte aligned.
@@ -152,83 +49,25 @@ __global__ void __launch_bounds__(kThreads, occupancy_for(R)) gf_locate_kernel(c
     const GfLaunch& a = sa.g;
     int s, w;
     wg_coords(a, s, w);
-    const int k = a.k;
-    const ECG_CONST CoefTab* T = cst(a.tabs);
     const uint8_t* sbase = stripe_base<MODE>(a, s);
     const long long ncols = a.B >> 4;  // < 2^27: B < 2^31
     const long long w0 = (long long)w * a.cols_per_wg;
     const int c0 = (int)w0, c1 = (int)min(w0 + (long long)a.cols_per_wg, ncols);
     const int lane = threadIdx.x & 63;
-
     unsigned mine[kSlots] = {0u, 0u, 0u};
-
     for (int cw = c0 + (int)(threadIdx.x & ~63u); cw < c1; cw += kThreads) {
         const int c = cw + lane;
+        // zeroed in place: through `= {}` or a helper R = 3, 4 take one VGPR more, and R = 4 INLINE loses a wave per SIMD
         uint32_t acc[R][4];
 #pragma unroll
         for (int p = 0; p < R; ++p)
 #pragma unroll
             for (int d = 0; d < 4; ++d) acc[p][d] = 0u;
-
-        if (c < c1) {
-            const long long off = (long long)c << 4;
-            int j = 0;
-            constexpr int LB = R >= 5 ? kGenWideLB : kGenLB;
-            for (; j + LB <= k; j += LB) {
-                uint32_t x[LB][4];
-#pragma unroll
-                for (int u = 0; u < LB; ++u) load16<1>(col_ptr<MODE>(a, sbase, j + u) + off, x[u]);
-                fold<R, LB, false>(x, T + (size_t)j * R, acc);
-            }
-            if constexpr (LB > 4) {  // the rest of k: four, two, one
-                if (j + 4 <= k) {
-                    uint32_t x[4][4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) load16<1>(col_ptr<MODE>(a, sbase, j + u) + off, x[u]);
-                    fold<R, 4, false>(x, T + (size_t)j * R, acc);
-                    j += 4;
-                }
-            }
-            if constexpr (LB > 2) {
-                if (j + 2 <= k) {
-                    uint32_t x[2][4];
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) load16<1>(col_ptr<MODE>(a, sbase, j + u) + off, x[u]);
-                    fold<R, 2, false>(x, T + (size_t)j * R, acc);
-                    j += 2;
-                }
-            }
-            if (j < k) {
-                uint32_t x[1][4];
-                load16<1>(col_ptr<MODE>(a, sbase, j) + off, x[0]);
-                fold<R, 1, false>(x, T + (size_t)j * R, acc);
-            }
-            if (sa.ident) {  // uniform.  acc[p] ^= the block row p checks
-                constexpr int IB = R < 4 ? R : 4;  // loads in flight, as a load batch
-#pragma unroll
-                for (int q0 = 0; q0 < R; q0 += IB) {
-                    uint32_t x[IB][4];
-#pragma unroll
-                    for (int u = 0; u < IB; ++u)
-                        if (q0 + u < R) load16<1>(ident_ptr<MODE>(sa, sbase, q0 + u) + off, x[u]);
-#pragma unroll
-                    for (int u = 0; u < IB; ++u)
-                        if (q0 + u < R) {
-#pragma unroll
-                            for (int d = 0; d < 4; ++d) acc[q0 + u][d] ^= x[u][d];
-                        }
-                }
-            }
-        }
-        uint32_t any = 0u;
-#pragma unroll
-        for (int p = 0; p < R; ++p)
-#pragma unroll
-            for (int d = 0; d < 4; ++d) any |= acc[p][d];
-        if (__ballot(any != 0u) == 0ull) continue;  // a clean wave column: the scrub's cost, nothing more
+        if (c < c1) syndromes16<R, MODE>(sa, sbase, (long long)c << 4, acc);
+        if (clean_wave(acc)) continue;  // a clean wave column: the scrub's cost, nothing more
         tally<R, 4>(sa, acc, lane, mine);
     }
-    post_votes(mine, sa.votes + (size_t)s * (size_t)(sa.n + 2), sa.n + 2, lane);
+    post_counters(mine, sa.votes + (size_t)s * (size_t)(sa.n + 2), sa.n + 2, lane);
 }
 
 // Byte path: bytes [off0, B) (tails, unaligned blocks).  cols_per_wg = bytes per workgroup.
@@ -237,8 +76,6 @@ __global__ void __launch_bounds__(kThreads) gf_locate_byte_kernel(const LocateLa
     const GfLaunch& a = sa.g;
     int s, w;
     wg_coords(a, s, w);
-    const int k = a.k;
-    const ECG_CONST CoefTab* T = cst(a.tabs);
     const long long b0 = a.off0 + (long long)w * a.cols_per_wg;
     const long long b1 = min(b0 + (long long)a.cols_per_wg, a.B);
     const uint8_t* sbase = stripe_base<MODE>(a, s);
@@ -246,28 +83,12 @@ __global__ void __launch_bounds__(kThreads) gf_locate_byte_kernel(const LocateLa
     unsigned mine[kSlots] = {0u, 0u, 0u};
     for (long long ow = b0 + (threadIdx.x & ~63); ow < b1; ow += kThreads) {
         const long long o = ow + lane;
-        uint32_t acc[R][1];
-#pragma unroll
-        for (int p = 0; p < R; ++p) acc[p][0] = 0u;
-        if (o < b1) {
-            for (int j = 0; j < k; ++j) {
-                const Split sp = split((uint32_t)col_ptr<MODE>(a, sbase, j)[o]);
-                const ECG_CONST CoefTab* t = T + (size_t)j * R;
-#pragma unroll
-                for (int p = 0; p < R; ++p) acc[p][0] ^= gmul(t[p], sp);
-            }
-            if (sa.ident) {
-#pragma unroll
-                for (int p = 0; p < R; ++p) acc[p][0] ^= ident_ptr<MODE>(sa, sbase, p)[o];
-            }
-        }
-        uint32_t any = 0u;
-#pragma unroll
-        for (int p = 0; p < R; ++p) any |= acc[p][0];
-        if (__ballot(any != 0u) == 0ull) continue;
+        uint32_t acc[R][1] = {};
+        if (o < b1) syndrome_byte<R, MODE>(sa, sbase, o, acc);
+        if (clean_wave(acc)) continue;
         tally<R, 1>(sa, acc, lane, mine);
     }
-    post_votes(mine, sa.votes + (size_t)s * (size_t)(sa.n + 2), sa.n + 2, lane);
+    post_counters(mine, sa.votes + (size_t)s * (size_t)(sa.n + 2), sa.n + 2, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -286,17 +107,7 @@ hipError_t launch_one(const LocateLaunch& a, dim3 g, hipStream_t st) {
 
 template <int MODE, bool BYTE>
 Launcher pick_r(int R) {
-    switch (R) {
-        case 1: return launch_one<1, MODE, BYTE>;
-        case 2: return launch_one<2, MODE, BYTE>;
-        case 3: return launch_one<3, MODE, BYTE>;
-        case 4: return launch_one<4, MODE, BYTE>;
-        case 5: return launch_one<5, MODE, BYTE>;
-        case 6: return launch_one<6, MODE, BYTE>;
-        case 7: return launch_one<7, MODE, BYTE>;
-        case 8: return launch_one<8, MODE, BYTE>;
-        default: return nullptr;
-    }
+    return pick_of8<1, Launcher>(R, nullptr, [](auto r) { return launch_one<decltype(r)::value, MODE, BYTE>; });
 }
 
 template <bool BYTE>
@@ -306,22 +117,13 @@ Launcher pick(int R, int mode) {
     return nullptr;
 }
 
-std::atomic<long long> g_locate_launched{0}, g_locate_read{0};
-// geometry of the most recent vector-path launch (locate_kernels.hpp kLocateLaunchFields), all zero before the first
-std::atomic<int> g_locate_last[kLocateLaunchFields];
+CheckLaunchLog g_locate_log;
 
 }  // namespace
 
-void locate_traffic(long long* launches, long long* bytes) {
-    if (launches) *launches = g_locate_launched.load(std::memory_order_relaxed);
-    if (bytes) *bytes = g_locate_read.load(std::memory_order_relaxed);
-}
+void locate_traffic(long long* launches, long long* bytes) { g_locate_log.traffic(launches, bytes); }
 
-int locate_last_launch(int* v, int cap) {
-    if (v && cap >= kLocateLaunchFields)
-        for (int i = 0; i < kLocateLaunchFields; ++i) v[i] = g_locate_last[i].load(std::memory_order_relaxed);
-    return kLocateLaunchFields;
-}
+int locate_last_launch(int* v, int cap) { return g_locate_log.last_launch(v, cap); }
 
 hipError_t launch_locate(const LocateLaunch& base, int mode, bool vec_ok, hipStream_t st) {
     const GfLaunch& b = base.g;
@@ -336,47 +138,19 @@ hipError_t launch_locate(const LocateLaunch& base, int mode, bool vec_ok, hipStr
     a.row_split = 0;
     a.prog_of_stripe = nullptr;
     const long long vec_bytes = vec_ok ? (a.B & ~15LL) : 0;
-    g_locate_launched.fetch_add((vec_bytes > 0) + (vec_bytes < a.B), std::memory_order_relaxed);
-    g_locate_read.fetch_add((long long)a.S * a.B * sa.n, std::memory_order_relaxed);
+    g_locate_log.count((vec_bytes > 0) + (vec_bytes < a.B), (long long)a.S * a.B * sa.n);
+    long long gx = 0;
     if (vec_bytes > 0) {
-        const long long ncols = vec_bytes >> 4;
-        long long cpw = get_option(ECG_OPT_COLS_PER_WG);
-        if (cpw <= 0) cpw = kThreads;  // 2 KiB of every block per workgroup, as the product and the scrub
-        if (ncols < cpw) cpw = ((ncols + kThreads - 1) / kThreads) * kThreads;
-        a.cols_per_wg = (int)cpw;
-        a.wg_per_stripe = (int)((ncols + cpw - 1) / cpw);
-        a.off0 = 0;
-        const long long gx = (long long)a.S * a.wg_per_stripe;
-        if (gx > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-        // The scrub's rule (scrub_kernels.hip launch_scrub): XCD-contiguous chunks, ECG_OPT_GRID_MAP 0 / 2 honoured.
-        long long gm = get_option(ECG_OPT_GRID_MAP);
-        if (gm == 3) gm = 1;
-        long long G = get_option(ECG_OPT_MAP_GROUP);
-        while (G > 1 && a.S % (8 * G) != 0) G >>= 1;
-        if (gm == 2 && a.S % (8 * G) != 0) gm = 1;
-        a.grid_map = (gm == 1 && gx % 8 == 0) ? 1 : (gm == 2) ? 2 : 0;
-        a.map_group = (int)G;
-        const int geo[kLocateLaunchFields] = {a.grid_map, a.map_group, a.cols_per_wg, a.wg_per_stripe, a.S, a.rtiles};
-        for (int i = 0; i < kLocateLaunchFields; ++i) g_locate_last[i].store(geo[i], std::memory_order_relaxed);
+        if (const hipError_t e = plan_vector_path(a, vec_bytes, g_locate_log, gx); e != hipSuccess) return e;
         Launcher l = pick<false>(a.m, mode);
         if (!l) return hipErrorInvalidValue;
-        const hipError_t e = l(sa, dim3((unsigned)gx), st);
-        if (e != hipSuccess) return e;
+        if (const hipError_t e = l(sa, dim3((unsigned)gx), st); e != hipSuccess) return e;
     }
     if (vec_bytes < a.B) {
-        const long long nbytes = a.B - vec_bytes;
-        long long bpw = 16LL * kThreads;
-        if (nbytes < bpw) bpw = ((nbytes + kThreads - 1) / kThreads) * kThreads;
-        a.cols_per_wg = (int)bpw;
-        a.wg_per_stripe = (int)((nbytes + bpw - 1) / bpw);
-        a.off0 = vec_bytes;
-        a.grid_map = 0;
-        const long long gx = (long long)a.S * a.wg_per_stripe;
-        if (gx > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+        if (const hipError_t e = plan_byte_path(a, vec_bytes, gx); e != hipSuccess) return e;
         Launcher l = pick<true>(a.m, mode);
         if (!l) return hipErrorInvalidValue;
-        const hipError_t e = l(sa, dim3((unsigned)gx), st);
-        if (e != hipSuccess) return e;
+        if (const hipError_t e = l(sa, dim3((unsigned)gx), st); e != hipSuccess) return e;
     }
     return hipSuccess;
 }

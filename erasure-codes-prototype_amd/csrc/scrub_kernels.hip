@@ -2,18 +2,18 @@
 //
 //   counts[s * r + p] = #{ x in [0, B) : XOR_j H[p][j] * in_j[x] != 0 }      (H: r x k check matrix)
 //
-// The data path is the region product's (gf_kernels.hip; shared pieces in gf_device.hpp): one lane per 16-byte
-// column, non-temporal dwordx4 loads, CoefTab tables in SGPRs, the same folds into MT accumulators, the same
-// load batches, workgroup -> chunk maps and occupancy hints.  Where the product stores its accumulators, the
+// The data path is the region product's (gf_kernels.hip; shared pieces in gf_device.hpp, and check_device.hpp for what
+// the locate and the heal share with this file): one lane per 16-byte column, non-temporal dwordx4 loads, CoefTab
+// tables in SGPRs, the same folds into MT accumulators, the same load batches (check_device.hpp fold_inputs),
+// workgroup -> chunk maps (check_launch.hpp) and occupancy hints.  Where the product stores its accumulators, the
 // check counts their nonzero bytes into MT per-lane counters (4 VALU ops per dword against ~18 per coefficient
 // for the fold); a wave whose counters are all zero is done, any other reduces them with shuffles and issues at
 // most one device-scope atomic add per row -- none where the sum is zero, so a clean stripe reads every byte
 // once and writes nothing.  Integer adds commute: the counts are exact and reproducible.
 // An encode-shaped check, H = [C | I], folds only C through the tables; row q's stored block is XORed in by one
 // v_bitop3 per dword (ScrubLaunch::ident): the check then costs the encode's arithmetic, not (k + m) / k of it.
-#include <atomic>
-
-#include "gf_device.hpp"
+#include "check_device.hpp"
+#include "check_launch.hpp"
 #include "scrub_kernels.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -24,14 +24,10 @@ namespace ecg {
 
 namespace {
 
-static_assert(kThreads % 64 == 0 && kMaxMTBin <= 64, "whole waves; one lane per row of a tile");
+static_assert(kMaxMTBin <= 64, "one lane per row of a tile");
 
-// Nonzero bytes of a dword: adding 0x7f to the low 7 bits of a byte carries into its bit 7 exactly when they
-// are not all zero (no carry leaves the byte), OR-ing x brings in bit 7 itself; one bit per nonzero byte is left.
-__device__ __forceinline__ unsigned nonzero_bytes(uint32_t x) {
-    const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-    return (unsigned)__popc((t | x) & 0x80808080u);
-}
+// Nonzero bytes of a dword: one bit per nonzero byte is left to count.
+__device__ __forceinline__ unsigned nonzero_bytes(uint32_t x) { return (unsigned)__popc(nonzero_mask(x)); }
 
 // Encode-shaped checks, H = [C | I] (ScrubLaunch::ident): the stored block of check row q, folded in after the C part.
 template <int MODE>
@@ -39,12 +35,6 @@ __device__ __forceinline__ const uint8_t* ident_ptr(const ScrubLaunch& sa, int s
     const GfLaunch& a = sa.g;
     if constexpr (MODE == GF_MODE_INLINE) return a.isrc[a.k + q];
     else return a.in_base + (long long)s * a.in_sstride + (long long)(sa.ident_base + q) * a.in_bstride;
-}
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // Per-lane counters -> counts[0, nrows), per wave.  A wave whose counters are all zero ends here (one ballot): no
@@ -96,35 +86,7 @@ __global__ void __launch_bounds__(kThreads, occupancy_for(MT)) gf_scrub_kernel(c
 #pragma unroll
             for (int d = 0; d < 4; ++d) acc[p][d] = 0u;
 
-        int j = 0;
-        constexpr int LB = BIN ? kLoadBatch : MT >= 5 ? kGenWideLB : kGenLB;
-        for (; j + LB <= k; j += LB) {
-            uint32_t x[LB][4];
-#pragma unroll
-            for (int u = 0; u < LB; ++u) load16<1>(src_ptr<MODE>(a, s, prog, j + u) + off, x[u]);
-            fold<MT, LB, BIN>(x, T + (size_t)j * MT, acc);
-        }
-        if constexpr (LB > 4) {  // the rest of k: four, two, one
-            if (j + 4 <= k) {
-                uint32_t x[4][4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) load16<1>(src_ptr<MODE>(a, s, prog, j + u) + off, x[u]);
-                fold<MT, 4, BIN>(x, T + (size_t)j * MT, acc);
-                j += 4;
-            }
-        }
-        if (j + 2 <= k) {
-            uint32_t x[2][4];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) load16<1>(src_ptr<MODE>(a, s, prog, j + u) + off, x[u]);
-            fold<MT, 2, BIN>(x, T + (size_t)j * MT, acc);
-            j += 2;
-        }
-        if (j < k) {
-            uint32_t x[1][4];
-            load16<1>(src_ptr<MODE>(a, s, prog, j) + off, x[0]);
-            fold<MT, 1, BIN>(x, T + (size_t)j * MT, acc);
-        }
+        fold_inputs<MT, BIN>(k, T, off, acc, [&](int j) { return src_ptr<MODE>(a, s, prog, j); });
         if (sa.ident) {  // uniform.  acc[p] ^= the block row p checks: one XOR per dword where a table fold takes ~18
             constexpr int IB = MT < 4 ? MT : 4;  // loads in flight, as a load batch
 #pragma unroll
@@ -216,39 +178,15 @@ hipError_t byte_launch(const ScrubLaunch& a, dim3 g, hipStream_t st) {
     return hipLaunchKernel((const void*)gf_scrub_byte_kernel<MT, MODE, BIN>, g, dim3(kThreads), argv, 0, st);
 }
 
-template <int MODE, bool BIN, bool BYTE, int MT>
-constexpr Launcher one() {
-    if constexpr (BYTE) return byte_launch<MT, MODE, BIN>;
-    else return vec_launch<MT, MODE, BIN>;
-}
-
 template <int MODE, bool BIN, bool BYTE>
 Launcher pick_mt(int MT) {
-    switch (MT) {
-        case 1: return one<MODE, BIN, BYTE, 1>();
-        case 2: return one<MODE, BIN, BYTE, 2>();
-        case 3: return one<MODE, BIN, BYTE, 3>();
-        case 4: return one<MODE, BIN, BYTE, 4>();
-        case 5: return one<MODE, BIN, BYTE, 5>();
-        case 6: return one<MODE, BIN, BYTE, 6>();
-        case 7: return one<MODE, BIN, BYTE, 7>();
-        case 8: return one<MODE, BIN, BYTE, 8>();
-        default: break;
-    }
-    if constexpr (BIN) {  // wide BINARY tiles (kMaxMTBin)
-        switch (MT) {
-            case 9: return one<MODE, BIN, BYTE, 9>();
-            case 10: return one<MODE, BIN, BYTE, 10>();
-            case 11: return one<MODE, BIN, BYTE, 11>();
-            case 12: return one<MODE, BIN, BYTE, 12>();
-            case 13: return one<MODE, BIN, BYTE, 13>();
-            case 14: return one<MODE, BIN, BYTE, 14>();
-            case 15: return one<MODE, BIN, BYTE, 15>();
-            case 16: return one<MODE, BIN, BYTE, 16>();
-            default: break;
-        }
-    }
-    return nullptr;
+    const auto one = [](auto mt) -> Launcher {
+        if constexpr (BYTE) return byte_launch<decltype(mt)::value, MODE, BIN>;
+        else return vec_launch<decltype(mt)::value, MODE, BIN>;
+    };
+    if constexpr (BIN)  // wide BINARY tiles (kMaxMTBin)
+        if (MT > 8) return pick_of8<9, Launcher>(MT, nullptr, one);
+    return pick_of8<1, Launcher>(MT, nullptr, one);
 }
 
 template <bool BYTE>
@@ -260,22 +198,13 @@ Launcher pick(const GfLaunch& a, int mode) {
     return nullptr;
 }
 
-std::atomic<long long> g_scrub_launched{0}, g_scrub_read{0};
-// geometry of the most recent vector-path launch (scrub_kernels.hpp kScrubLaunchFields), all zero before the first
-std::atomic<int> g_scrub_last[kScrubLaunchFields];
+CheckLaunchLog g_scrub_log;
 
 }  // namespace
 
-void scrub_traffic(long long* launches, long long* bytes) {
-    if (launches) *launches = g_scrub_launched.load(std::memory_order_relaxed);
-    if (bytes) *bytes = g_scrub_read.load(std::memory_order_relaxed);
-}
+void scrub_traffic(long long* launches, long long* bytes) { g_scrub_log.traffic(launches, bytes); }
 
-int scrub_last_launch(int* v, int cap) {
-    if (v && cap >= kScrubLaunchFields)
-        for (int i = 0; i < kScrubLaunchFields; ++i) v[i] = g_scrub_last[i].load(std::memory_order_relaxed);
-    return kScrubLaunchFields;
-}
+int scrub_last_launch(int* v, int cap) { return g_scrub_log.last_launch(v, cap); }
 
 hipError_t launch_scrub(const ScrubLaunch& base, int mode, bool vec_ok, hipStream_t st) {
     const GfLaunch& b = base.g;
@@ -289,49 +218,20 @@ hipError_t launch_scrub(const ScrubLaunch& base, int mode, bool vec_ok, hipStrea
     GfLaunch& a = sa.g;
     a.row_split = 0;
     const long long vec_bytes = vec_ok ? (a.B & ~15LL) : 0;
-    g_scrub_launched.fetch_add((vec_bytes > 0) + (vec_bytes < a.B), std::memory_order_relaxed);
-    g_scrub_read.fetch_add((long long)a.S * a.B * ((long long)a.rtiles * a.k + (sa.ident ? a.m : 0)),
-                           std::memory_order_relaxed);
+    g_scrub_log.count((vec_bytes > 0) + (vec_bytes < a.B),
+                      (long long)a.S * a.B * ((long long)a.rtiles * a.k + (sa.ident ? a.m : 0)));
+    long long gx = 0;
     if (vec_bytes > 0) {
-        const long long ncols = vec_bytes >> 4;
-        long long cpw = get_option(ECG_OPT_COLS_PER_WG);
-        if (cpw <= 0) cpw = kThreads;  // 2 KiB of every block per workgroup, as the product
-        if (ncols < cpw) cpw = ((ncols + kThreads - 1) / kThreads) * kThreads;
-        a.cols_per_wg = (int)cpw;
-        a.wg_per_stripe = (int)((ncols + cpw - 1) / cpw);
-        a.off0 = 0;
-        const long long gx = (long long)a.S * a.wg_per_stripe;
-        if (gx > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-        // The auto rule is the product's for outputs inside the input stripes (XCD-contiguous chunks): the check
-        // reads what an encode into the stripe reads.  ECG_OPT_GRID_MAP 0 / 2 are honoured as there.
-        long long gm = get_option(ECG_OPT_GRID_MAP);
-        if (gm == 3) gm = 1;
-        long long G = get_option(ECG_OPT_MAP_GROUP);
-        while (G > 1 && a.S % (8 * G) != 0) G >>= 1;
-        if (gm == 2 && a.S % (8 * G) != 0) gm = 1;
-        a.grid_map = (gm == 1 && gx % 8 == 0) ? 1 : (gm == 2) ? 2 : 0;
-        a.map_group = (int)G;
-        const int geo[kScrubLaunchFields] = {a.grid_map, a.map_group, a.cols_per_wg, a.wg_per_stripe, a.S, a.rtiles};
-        for (int i = 0; i < kScrubLaunchFields; ++i) g_scrub_last[i].store(geo[i], std::memory_order_relaxed);
+        if (const hipError_t e = plan_vector_path(a, vec_bytes, g_scrub_log, gx); e != hipSuccess) return e;
         Launcher l = pick<false>(a, mode);
         if (!l) return hipErrorInvalidValue;
-        const hipError_t e = l(sa, dim3((unsigned)gx, (unsigned)a.rtiles), st);
-        if (e != hipSuccess) return e;
+        if (const hipError_t e = l(sa, dim3((unsigned)gx, (unsigned)a.rtiles), st); e != hipSuccess) return e;
     }
     if (vec_bytes < a.B) {
-        const long long nbytes = a.B - vec_bytes;
-        long long bpw = 16LL * kThreads;
-        if (nbytes < bpw) bpw = ((nbytes + kThreads - 1) / kThreads) * kThreads;
-        a.cols_per_wg = (int)bpw;
-        a.wg_per_stripe = (int)((nbytes + bpw - 1) / bpw);
-        a.off0 = vec_bytes;
-        a.grid_map = 0;
-        const long long gx = (long long)a.S * a.wg_per_stripe;
-        if (gx > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+        if (const hipError_t e = plan_byte_path(a, vec_bytes, gx); e != hipSuccess) return e;
         Launcher l = pick<true>(a, mode);
         if (!l) return hipErrorInvalidValue;
-        const hipError_t e = l(sa, dim3((unsigned)gx, (unsigned)a.rtiles), st);
-        if (e != hipSuccess) return e;
+        if (const hipError_t e = l(sa, dim3((unsigned)gx, (unsigned)a.rtiles), st); e != hipSuccess) return e;
     }
     return hipSuccess;
 }

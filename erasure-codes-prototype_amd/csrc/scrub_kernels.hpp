@@ -25,10 +25,10 @@ hipError_t launch_scrub(const ScrubLaunch& base, int mode, bool vec_ok, hipStrea
 // Scrub kernels launched in this process, and the bytes they read as planned (S * B * k per row tile, plus S * B * m
 // for the identity part of an encode-shaped check).
 void scrub_traffic(long long* launches, long long* bytes);
-// Geometry of this process's most recent vector-path launch, as placed in its descriptor after the fallbacks:
-// grid_map, map_group, cols_per_wg, wg_per_stripe, S, rtiles (all zero before the first).  Returns the field count;
-// v is written when cap suffices.  A diagnostic for tests: it says which workgroup -> chunk map a call ran.
-constexpr int kScrubLaunchFields = 6;
+// Geometry of this process's most recent vector-path launch, as placed in its descriptor after the fallbacks
+// (check_launch.hpp CheckLaunchLog): grid_map, map_group, cols_per_wg, wg_per_stripe, S, rtiles (all zero before the
+// first).  Returns the field count; v is written when cap suffices.  A diagnostic for tests: it says which
+// workgroup -> chunk map a call ran.
 int scrub_last_launch(int* v, int cap);
 
 }  // namespace ecg
