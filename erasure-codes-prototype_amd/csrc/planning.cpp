@@ -3,12 +3,14 @@
 // A partition is the set of a stripe's blocks placed in one cluster; a repair plan lists, per failed
 // set, the blocks each cluster contributes (each inner vector becomes one partial-decoding call at a
 // helper proxy, handle_repair.cpp:169-176).  Host-only integer logic, restated from the reference's
-// control flow (file:line per method).  Two deliberate, documented differences:
-//   * ties in the "largest partition first" orderings are broken stably (std::stable_sort); the
-//     reference uses std::sort, which libstdc++ implements as a stable insertion sort for <= 16
-//     elements (every BASELINE configuration) and leaves unspecified above that;
+// control flow (file:line per method).  One deliberate, documented difference:
 //   * random placement draws from a per-object splitmix64 stream instead of a fresh
 //     random_device-seeded mt19937 per draw (utils.cpp:6-21): same support, uniform, reproducible.
+// The "largest partition first" orderings use std::sort under the reference's comparator, as the
+// reference does: it ties on equal sizes, so above 16 elements (where libstdc++ leaves insertion
+// sort) which helper comes first among equals is std::sort's own order.  The reference's classes
+// show that order (tests/golden/reference_ec.json, e.g. RS(30,3) under FLAT placement), so a stable
+// sort here would name other helpers than the reference does.
 #include <algorithm>
 #include <random>
 
@@ -22,7 +24,7 @@ bool cmp_descending(const std::pair<int, int>& a, const std::pair<int, int>& b) 
     return a.second > b.second;
 }
 
-void sort_descending(std::vector<std::pair<int, int>>& v) { std::stable_sort(v.begin(), v.end(), cmp_descending); }
+void sort_descending(std::vector<std::pair<int, int>>& v) { std::sort(v.begin(), v.end(), cmp_descending); }
 
 bool contains(const std::vector<int>& v, int x) { return std::find(v.begin(), v.end(), x) != v.end(); }
 

@@ -7,11 +7,11 @@ generate_repair_plan with its help-block selection (rs.cpp:118-279, lrc.cpp:240-
 pc.cpp:451-551 / 1166-1264).  Used by tests/test_planning.py to pin csrc/planning.cpp.
 
 Parity status: the reference's planning is self-contained C++ (no Jerasure), so this restatement is
-checked line by line against its source; no reference build exists here, hence no
-reference-generated golden plans — the hand-derived expectations in tests/test_planning.py (the
-SURVEY.md §8(d) config-3 partition, RS/PC examples worked by hand) pin it.
+checked line by line against its source, and pinned by the plans the reference's own classes returned
+(tests/golden/reference_ec.json, tests/test_reference_ec.py) besides the hand-derived expectations in
+tests/test_planning.py (the SURVEY.md §8(d) config-3 partition, RS/PC examples worked by hand).
 Two conventions shared with the product and documented there:
-  * "largest first" orderings are stable (std::sort in libstdc++ is stable for <= 16 elements);
+  * "largest first" orderings are libstdc++'s std::sort, ties included (_std_sort below; stable up to 16 elements);
   * random placement uses the splitmix64 stream below instead of random_device-seeded mt19937.
 """
 from __future__ import annotations
@@ -29,9 +29,76 @@ class RepairPlan:  # erasure_code.h:53-58
     help_blocks: list = field(default_factory=list)
 
 
+def _std_sort(v, comp):
+    """std::sort as libstdc++ implements it (bits/stl_algo.h: __introsort_loop with its 16-element threshold and
+    median-of-three pivot moved to the front, then __final_insertion_sort), in place.  The reference sorts its
+    (partition, size) pairs with it under a comparator that ties on equal sizes (utils.cpp:159-162), so above 16
+    elements the order of the ties -- and with it which helpers a plan names first -- is this algorithm's, and the
+    reference's own classes (tests/golden/reference_ec.json) show exactly that order.  Up to 16 elements it is a
+    stable insertion sort.  The heapsort the loop falls back to after 2 * floor(log2 n) bad splits is not restated."""
+    n = len(v)
+
+    def linear_insert(last):  # __unguarded_linear_insert
+        val = v[last]
+        nxt = last - 1
+        while comp(val, v[nxt]):
+            v[last] = v[nxt]
+            last = nxt
+            nxt -= 1
+        v[last] = val
+
+    def insertion(first, last):  # __insertion_sort
+        for i in range(first + 1, last):
+            if comp(v[i], v[first]):
+                val = v[i]
+                v[first + 1:i + 1] = v[first:i]
+                v[first] = val
+            else:
+                linear_insert(i)
+
+    def median_to_first(result, a, b, c):  # __move_median_to_first
+        if comp(v[a], v[b]):
+            pick = b if comp(v[b], v[c]) else (c if comp(v[a], v[c]) else a)
+        else:
+            pick = a if comp(v[a], v[c]) else (c if comp(v[b], v[c]) else b)
+        v[result], v[pick] = v[pick], v[result]
+
+    def partition(first, last, pivot):  # __unguarded_partition
+        while True:
+            while comp(v[first], v[pivot]):
+                first += 1
+            last -= 1
+            while comp(v[pivot], v[last]):
+                last -= 1
+            if not first < last:
+                return first
+            v[first], v[last] = v[last], v[first]
+            first += 1
+
+    def loop(first, last, depth):  # __introsort_loop
+        while last - first > 16:
+            if depth == 0:
+                raise NotImplementedError("std::sort's heapsort fallback")
+            depth -= 1
+            median_to_first(first, first + 1, first + (last - first) // 2, last - 1)
+            cut = partition(first + 1, last, first)
+            loop(cut, last, depth)
+            last = cut
+
+    if n:
+        loop(0, n, 2 * (n.bit_length() - 1))
+        if n > 16:  # __final_insertion_sort
+            insertion(0, 16)
+            for i in range(16, n):
+                linear_insert(i)
+        else:
+            insertion(0, n)
+    return v
+
+
 def _desc(pairs):
-    """std::sort(..., cmp_descending) (utils.cpp:159-162) as a stable sort on .second."""
-    return sorted(pairs, key=lambda p: -p[1])
+    """std::sort(..., cmp_descending) (utils.cpp:159-162): descending on .second, ties as libstdc++ leaves them."""
+    return _std_sort(list(pairs), lambda a, b: a[1] > b[1])
 
 
 class Planner:

@@ -4,8 +4,9 @@ Option A relinks the reference's unchanged EC layer (project/src/ec/{erasure_cod
 against libecg by putting include/jerasure_shim/ first on the include path.  This compiles each of those
 files with `g++ -std=c++20 -fsyntax-only` (the reference's own standard, project/CmakeLists.txt) against
 the shim headers: every Jerasure call it makes must resolve to a shim declaration with a compatible
-signature.  -fsyntax-only writes no object and runs nothing; the reference is never built or executed
-here, and /root/reference does not exist on the GPU box, so the test skips there.
+signature.  -fsyntax-only writes no object; the build and the run of those sources are oracle/Makefile's
+(oracle/_ref/ref_ec_cpu, ref_ec_gpu) and tests/test_reference_ec.py / tests/test_gpu_reference_ec.py's.
+/root/reference does not exist on the GPU box, so this test skips there.
 """
 import json
 import os
