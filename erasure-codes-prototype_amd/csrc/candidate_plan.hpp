@@ -1,14 +1,15 @@
-// The candidate plan of a check matrix H, and the host steps from a plan to its launch descriptor, shared by the entry
-// points that test "does block b alone explain this syndrome?": locate.cpp (libecg_locate.so) and heal.cpp
-// (libecg_heal.so).  Header-only; no kernel launch and no state.
+// The candidate plan of a check matrix H, the heal plan on top of it, and the host steps from a plan to its launch
+// descriptor, shared by the entry points that test "does block b alone explain this syndrome?": locate.cpp
+// (libecg_locate.so), heal.cpp (libecg_heal.so) and heal2.cpp (libecg_heal2.so).  Header-only; no kernel launch and no
+// state.
 #pragma once
 #include <string.h>
 
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "capi_handle.hpp"
 #include "check_common.hpp"
 #include "gf256.hpp"
 #include "locate_kernels.hpp"
@@ -42,10 +43,33 @@ inline CandidatePlan make_plan(int n, int r, const int* H, const int* src_ids, b
     return pl;
 }
 
-// The refusal of a check one lane cannot hold, in the words of library `lib`; `tail` ends its advice.
+inline unsigned pivot_of(const CandidatePlan& pl, int b) { return (pl.p0[b >> 3] >> ((b & 7) * 4)) & 15u; }
+
+// What a correction needs on top of the candidate test: the error value is s_p0 / H[p0(b)][b].
+struct HealPlan {
+    CandidatePlan cand;
+    LinearOp inv;  // 1 x n: 1 / H[p0(b)][b]; 0 for a zero column of H
+};
+
+inline HealPlan make_heal_plan(int n, int r, const int* H, const int* src_ids, bool consecutive) {
+    HealPlan hp;
+    hp.cand = make_plan(n, r, H, src_ids, consecutive);
+    hp.inv.src_ids = iota(n);
+    hp.inv.dst_ids = iota(1);
+    hp.inv.coef.assign((size_t)n, 0);
+    for (int b = 0; b < n; b++) {
+        const unsigned p0 = pivot_of(hp.cand, b);
+        if (p0 != kNoPivot) hp.inv.coef[b] = (uint8_t)gf::inv(H[(size_t)p0 * n + b] & 0xff);
+    }
+    return hp;
+}
+
+// ECG_OK for a check one lane can hold (r <= kMaxMT, n <= kInlineSrc), else its refusal in the words of library `lib`;
+// `tail` ends the advice.
 struct TooLarge {
     const char *lib, *tail;
     int operator()(long long n, int r) const {
+        if (r <= kMaxMT && n <= kInlineSrc) return ECG_OK;
         set_last_error(std::string(lib) + ": r = " + std::to_string(r) + ", n = " + std::to_string(n) +
                        " exceeds r <= " + std::to_string(kMaxMT) + ", n <= " + std::to_string(kInlineSrc) +
                        " (one lane holds all r syndromes); product codes stay with ecg_scrub_suspects" + tail);
@@ -53,36 +77,40 @@ struct TooLarge {
     }
 };
 
-// The check matrix of an ErasureCode handle, r x n: ECG_OK, the code's own error, or the refusal of too large a one.
-inline int ec_check(ecg_ec* ec, const TooLarge& too_large, std::vector<int>& H, int& n, int& r) {
-    r = ec->impl->check_matrix(H);
-    if (r < 0) return r;
-    if (r < 1) return ECG_EINVAL;
-    n = (int)(H.size() / (size_t)r);
-    return r > kMaxMT || n > kInlineSrc ? too_large(n, r) : ECG_OK;
-}
-
-// The table sets a candidate launch reads; the caller notes the launch on each (Engine::note_launch).
+// The table sets a candidate launch reads: the check's, the ratios', then those of the caller's further ops.
 struct CandidateTables {
-    std::shared_ptr<ProgramSet> chk, ratio;
+    std::shared_ptr<ProgramSet> set[4];
+    int count = 0;
+    const ProgramSet& extra(int i) const { return *set[2 + i]; }
+    void note_launch(hipStream_t st) const {
+        for (int i = 0; i < count; i++) Engine::instance().note_launch(*set[i], st);
+    }
 };
 
-// The LocateLaunch of a plan, up to the launch: flush the thread's batch scope, fetch the check's and the ratios'
-// tables, fill `a` (`fill` sets its sources) and zero the S x (n + 2) counters; `zeroing` labels a failure of that.
+// The LocateLaunch of a plan, up to the launch: flush the thread's batch scope, fetch the tables of the check, of the
+// ratios and of `extra` (at most two ops, one row tile each) into `t`, fill `a` (`fill` sets its sources) and zero the
+// S x ncounters counters; `zeroing` labels a failure of that.
 template <class Fill>
-int prepare_launch(const CandidatePlan& pl, long long B, int S, const int* d_stripe_ids, unsigned* d_counters,
-                   const char* zeroing, hipStream_t st, Fill fill, LocateLaunch& a, CandidateTables& t) {
+int prepare_launch(const CandidatePlan& pl, std::initializer_list<const LinearOp*> extra, int ncounters, long long B,
+                   int S, const int* d_stripe_ids, unsigned* d_counters, const char* zeroing, hipStream_t st, Fill fill,
+                   LocateLaunch& a, CandidateTables& t) {
     if (const int rc = batch_flush_pending(); rc != ECG_OK) return rc;
-    Engine& eng = Engine::instance();
+    const LinearOp* ops[4] = {&pl.chk.op, &pl.ratio};
+    t.count = 2;
+    for (const LinearOp* op : extra) ops[t.count++] = op;
     int status = ECG_OK;
-    t.chk = eng.program_set(&pl.chk.op, 1, &status, st);
-    if (!t.chk) return status;
-    t.ratio = eng.program_set(&pl.ratio, 1, &status, st);
-    if (!t.ratio) return status;
-    if (const int rc = t.chk->ensure_ready(st); rc != ECG_OK) return rc;
-    if (const int rc = t.ratio->ensure_ready(st); rc != ECG_OK) return rc;
-    const ProgramSet &ps = *t.chk, &rs = *t.ratio;
-    if (ps.MT != pl.r || ps.rtiles != 1 || rs.MT != pl.r || rs.rtiles != 1 || rs.k != pl.n) return ECG_EINVAL;
+    for (int i = 0; i < t.count; i++) {
+        t.set[i] = Engine::instance().program_set(ops[i], 1, &status, st);
+        if (!t.set[i]) return status;
+    }
+    for (int i = 0; i < t.count; i++)
+        if (const int rc = t.set[i]->ensure_ready(st); rc != ECG_OK) return rc;
+    const ProgramSet &ps = *t.set[0], &rs = *t.set[1];
+    if (ps.MT != pl.r || ps.rtiles != 1) return ECG_EINVAL;
+    for (int i = 1; i < t.count; i++)
+        if (t.set[i]->MT != (int)ops[i]->dst_ids.size() || t.set[i]->rtiles != 1 ||
+            t.set[i]->k != (int)ops[i]->src_ids.size())
+            return ECG_EINVAL;
     memset(&a, 0, sizeof(a));
     a.g.tabs = ps.d_tabs;
     a.g.src_ids = ps.d_src;
@@ -102,7 +130,7 @@ int prepare_launch(const CandidatePlan& pl, long long B, int S, const int* d_str
     a.n = pl.n;
     memcpy(a.p0, pl.p0, sizeof(a.p0));
     fill(a.g);
-    if (const hipError_t e = hipMemsetAsync(d_counters, 0, (size_t)S * (size_t)(pl.n + 2) * sizeof(unsigned), st);
+    if (const hipError_t e = hipMemsetAsync(d_counters, 0, (size_t)S * (size_t)ncounters * sizeof(unsigned), st);
         e != hipSuccess)
         return hip_fail(e, zeroing);
     return ECG_OK;

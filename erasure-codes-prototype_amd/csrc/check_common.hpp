@@ -1,12 +1,15 @@
 // Host-side pieces shared by the entry points over a check matrix H: scrub.cpp (libecg_scrub.so), locate.cpp
-// (libecg_locate.so) and heal.cpp (libecg_heal.so).  Header-only; no HIP launch and no state.
+// (libecg_locate.so), heal.cpp (libecg_heal.so) and heal2.cpp (libecg_heal2.so).  Header-only; no HIP launch and no
+// state.
 #pragma once
 #include <stdint.h>
 
 #include <string>
 #include <vector>
 
+#include "capi_handle.hpp"
 #include "engine.hpp"
+#include "gf_kernels.hpp"
 
 namespace ecg {
 
@@ -66,5 +69,49 @@ inline std::vector<int> iota(int n) {
     for (int i = 0; i < n; i++) v[i] = i;
     return v;
 }
+
+// The check matrix of an ErasureCode handle, r x n: ECG_OK, the code's own error, or what `refuse(n, r)` makes of its
+// size (ECG_OK, or the library's refusal).
+template <class Refuse>
+int ec_check(ecg_ec* ec, Refuse refuse, std::vector<int>& H, int& n, int& r) {
+    r = ec->impl->check_matrix(H);
+    if (r < 0) return r;
+    if (r < 1) return ECG_EINVAL;
+    n = (int)(H.size() / (size_t)r);
+    return refuse(n, r);
+}
+
+// The sources of a strided form, S stripes of blocks at d_base + s * sstride + b * bstride: whether the vector path
+// may read them, and (called with the launch's GfLaunch) their place in the descriptor.
+struct StridedSrc {
+    const void* d_base;
+    long long sstride, bstride;
+    bool vec_ok() const { return aligned16(d_base) && sstride % 16 == 0 && bstride % 16 == 0; }
+    void operator()(GfLaunch& g) const {
+        g.in_base = (const uint8_t*)d_base;
+        g.in_sstride = sstride;
+        g.in_bstride = bstride;
+    }
+};
+
+// The sources of a single-stripe `_ec` form: block b < k is d_data_ptrs[b], block b >= k is d_coding_ptrs[b - k].
+struct BlockPtrs {
+    int k, n;
+    char **d_data_ptrs, **d_coding_ptrs;
+    const void* at(int b) const { return b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k]; }
+    bool any_null() const {
+        for (int b = 0; b < n; b++)
+            if (!at(b)) return true;
+        return false;
+    }
+    bool vec_ok() const {
+        bool ok = true;
+        for (int b = 0; b < n; b++) ok &= aligned16(at(b));
+        return ok;
+    }
+    void operator()(GfLaunch& g) const {
+        for (int b = 0; b < n; b++) g.isrc[b] = (const uint8_t*)at(b);
+    }
+};
 
 }  // namespace ecg

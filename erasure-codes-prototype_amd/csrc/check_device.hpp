@@ -1,11 +1,13 @@
 // Device-side pieces shared by the kernels over a check matrix H: the scrub (scrub_kernels.hip), the locate
-// (locate_kernels.hip) and the heal (heal_kernels.hip), on top of gf_device.hpp.  Each library compiles them into its
-// own code object.  Everything here is inlined into the kernels that use it; the header defines no kernel and no host
-// state.
+// (locate_kernels.hip), the heal (heal_kernels.hip) and heal2 (heal2_kernels.hip), on top of gf_device.hpp.  Each
+// library compiles them into its own code object.  Everything here is inlined into the kernels that use it; the header
+// defines no kernel and no host state.
 //
-//   all three          fold_inputs (the load-batch ladder), nonzero_mask, wave_sum
-//   locate and heal    the syndrome phase (syndromes16, syndrome_byte, clean_wave), the candidate loop, the n + 2
-//                      counters of a wave in three registers (credit, post_counters) and the block pointers
+//   all four                 fold_inputs (the load-batch ladder), nonzero_mask, wave_sum
+//   locate, heal and heal2   the syndrome phase (syndromes16, syndrome_byte, clean_wave), the candidate loop (heal2: in
+//                            a copy that keeps the masks), the counters of a wave in three registers (credit,
+//                            post_counters) and the block pointers
+//   heal and heal2           block_ptr, byte_mask: where and under which mask a correction is written
 #pragma once
 #include "gf_device.hpp"
 #include "locate_kernels.hpp"
@@ -69,7 +71,7 @@ __device__ __forceinline__ void fold_inputs(int k, const ECG_CONST CoefTab* T, l
 }
 
 // ---------------------------------------------------------------------------------------------
-// Locate and heal: one lane holds all R syndromes of its column (one row tile, GENERAL flavour).
+// Locate, heal and heal2: one lane holds all R syndromes of its column (one row tile, GENERAL flavour).
 
 // Block pointers.  STRIDED: `sbase` is the selected stripe's base, in_base + stripe_of[s] * in_sstride, worked out once
 // per workgroup (gf_device.hpp src_ptr tests stripe_of at every load); INLINE: the pointers in the kernel arguments.
@@ -95,6 +97,14 @@ template <int MODE>
 __device__ __forceinline__ const uint8_t* ident_ptr(const LocateLaunch& sa, const uint8_t* sbase, int q) {
     if constexpr (MODE == GF_MODE_INLINE) return sa.g.isrc[sa.g.k + q];
     else return sbase + (long long)(sa.ident_base + q) * sa.g.in_bstride;
+}
+
+// Block b, to be written (heal, heal2): a table column, or -- the last R blocks of an [C | I] check, which the tables
+// do not hold -- the stored block of check row b - k.  b is uniform.
+template <int MODE>
+__device__ __forceinline__ uint8_t* block_ptr(const LocateLaunch& sa, const uint8_t* sbase, int b) {
+    const uint8_t* p = b < sa.g.k ? col_ptr<MODE>(sa.g, sbase, b) : ident_ptr<MODE>(sa, sbase, b - sa.g.k);
+    return const_cast<uint8_t*>(p);
 }
 
 // acc ^= the R syndromes of the 16-byte column at byte `off` of the stripe's blocks (vector path).
@@ -149,6 +159,9 @@ __device__ __forceinline__ bool clean_wave(const uint32_t (&syn)[R][W]) {
         for (int d = 0; d < W; ++d) any |= syn[p][d];
     return __ballot(any != 0u) == 0ull;
 }
+
+// 0x80 bits -> 0xff bytes
+__device__ __forceinline__ uint32_t byte_mask(uint32_t m) { return (m >> 7) * 0xffu; }
 
 // counter idx += tot, in the lane that owns it: lane i of register j owns counter 64 j + i (idx and tot are uniform)
 __device__ __forceinline__ void credit(unsigned (&mine)[kSlots], int idx, unsigned tot, int lane) {

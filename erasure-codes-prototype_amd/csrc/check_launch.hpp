@@ -1,6 +1,7 @@
-// The host-side launch rule shared by launch_scrub, launch_locate and launch_heal (scrub_kernels.hip,
-// locate_kernels.hip, heal_kernels.hip): how bytes [0, B) of S launch stripes are dealt to workgroups, and what each
-// library records about its launches.  Host-only and header-only; every library owns one CheckLaunchLog.
+// The host-side launch rule shared by launch_scrub, launch_locate, launch_heal and launch_heal2 (scrub_kernels.hip,
+// locate_kernels.hip, heal_kernels.hip, heal2_kernels.hip): how bytes [0, B) of S launch stripes are dealt to
+// workgroups, the vector-then-byte launch sequence, the run-time choice of a kernel instantiation, and what each library
+// records about its launches.  Host-only and header-only; every library owns one CheckLaunchLog.
 #pragma once
 #include <atomic>
 #include <type_traits>
@@ -89,6 +90,52 @@ T pick_of8(int n, T none, F f) {
         case 7: return f(std::integral_constant<int, LO + 7>());
         default: return none;
     }
+}
+
+// What every launch_* does once its descriptor copy `a` has passed the library's own checks: count the launches and
+// the `planned` bytes they read in `log`, then the vector path over the 16-byte columns (if vec_ok) and the byte path
+// over what is left.  vec(grid) and byte(grid) launch the library's kernel for `a` as it then stands; gy is the grid's
+// y dimension (the scrub's row tiles, else 1).
+template <class Vec, class Byte>
+hipError_t launch_paths(GfLaunch& a, bool vec_ok, CheckLaunchLog& log, long long planned, int gy, Vec vec, Byte byte) {
+    const long long vec_bytes = vec_ok ? (a.B & ~15LL) : 0;
+    log.count((vec_bytes > 0) + (vec_bytes < a.B), planned);
+    long long gx = 0;
+    if (vec_bytes > 0) {
+        if (const hipError_t e = plan_vector_path(a, vec_bytes, log, gx); e != hipSuccess) return e;
+        if (const hipError_t e = vec(dim3((unsigned)gx, (unsigned)gy)); e != hipSuccess) return e;
+    }
+    if (vec_bytes < a.B) {
+        if (const hipError_t e = plan_byte_path(a, vec_bytes, gx); e != hipSuccess) return e;
+        if (const hipError_t e = byte(dim3((unsigned)gx, (unsigned)gy)); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// One workgroup shape for every check kernel; a null kernel (no instantiation for the descriptor) is an error.
+template <class Launch>
+hipError_t launch_kernel(const void* kernel, const Launch& a, dim3 grid, hipStream_t st) {
+    if (!kernel) return hipErrorInvalidValue;
+    void* argv[] = {(void*)&a};
+    return hipLaunchKernel(kernel, grid, dim3(kThreads), argv, 0, st);
+}
+
+// The kernel of a candidate-test library for R check rows, LO <= R <= kMaxMT, or null.  K::kernel<R, MODE, BYTE>() names
+// the library's instantiations (locate, heal and heal2 each define such a K).
+template <class K, int LO, int MODE, bool BYTE>
+const void* candidate_kernel_of(int R) {
+    return pick_of8<LO, const void*>(R, nullptr, [](auto r) -> const void* {
+        constexpr int RR = decltype(r)::value;
+        if constexpr (RR <= kMaxMT) return K::template kernel<RR, MODE, BYTE>();
+        else return nullptr;
+    });
+}
+
+template <class K, int LO, bool BYTE>
+const void* candidate_kernel(int R, int mode) {
+    if (mode == GF_MODE_INLINE) return candidate_kernel_of<K, LO, GF_MODE_INLINE, BYTE>(R);
+    if (mode == GF_MODE_STRIDED) return candidate_kernel_of<K, LO, GF_MODE_STRIDED, BYTE>(R);
+    return nullptr;
 }
 
 }  // namespace ecg

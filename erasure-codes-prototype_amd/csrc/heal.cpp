@@ -19,26 +19,6 @@ using namespace ecg;
 
 namespace {
 
-struct HealPlan {
-    CandidatePlan cand;
-    LinearOp inv;  // 1 x n: 1 / H[p0(b)][b]; 0 for a zero column of H
-};
-
-unsigned pivot_of(const CandidatePlan& pl, int b) { return (pl.p0[b >> 3] >> ((b & 7) * 4)) & 15u; }
-
-HealPlan make_heal_plan(int n, int r, const int* H, const int* src_ids, bool consecutive) {
-    HealPlan hp;
-    hp.cand = make_plan(n, r, H, src_ids, consecutive);
-    hp.inv.src_ids = iota(n);
-    hp.inv.dst_ids = iota(1);
-    hp.inv.coef.assign((size_t)n, 0);
-    for (int b = 0; b < n; b++) {
-        const unsigned p0 = pivot_of(hp.cand, b);
-        if (p0 != kNoPivot) hp.inv.coef[b] = (uint8_t)gf::inv(H[(size_t)p0 * n + b] & 0xff);
-    }
-    return hp;
-}
-
 // Two nonzero columns of H are proportional exactly when they have the same pivot row and the same ratio column.
 // Returns false, with a < b the first such pair, or true when every bad position has at most one explaining block.
 bool columns_distinct(const CandidatePlan& pl, int& a_out, int& b_out) {
@@ -71,32 +51,23 @@ int check_any(const CandidatePlan& pl) {
     return ECG_EINVAL;
 }
 
-// The locate's launch descriptor with the report zeroed (candidate_plan.hpp prepare_launch), the pivot inverses' tables
-// and the candidate set on top of it, then the launch.  `fill` sets the launch's sources.
+// The locate's launch descriptor with the report zeroed (candidate_plan.hpp prepare_launch, which fetches the pivot
+// inverses' tables with the others), the candidate set on top of it, then the launch.  `fill` sets the launch's sources.
 template <class Fill>
 int run_heal(const HealPlan& hp, int mode, long long B, int S, const int* d_stripe_ids, const int* d_targets,
              int target, bool any, unsigned* d_report, bool vec_ok, hipStream_t st, Fill fill) {
     HealLaunch h;
-    memset(&h, 0, sizeof(h));
     CandidateTables t;
-    if (const int rc =
-            prepare_launch(hp.cand, B, S, d_stripe_ids, d_report, "hipMemsetAsync(heal report)", st, fill, h.l, t);
+    if (const int rc = prepare_launch(hp.cand, {&hp.inv}, hp.cand.n + 2, B, S, d_stripe_ids, d_report,
+                                      "hipMemsetAsync(heal report)", st, fill, h.l, t);
         rc != ECG_OK)
         return rc;
-    Engine& eng = Engine::instance();
-    int status = ECG_OK;
-    std::shared_ptr<ProgramSet> is = eng.program_set(&hp.inv, 1, &status, st);
-    if (!is) return status;
-    if (const int rc = is->ensure_ready(st); rc != ECG_OK) return rc;
-    if (is->MT != 1 || is->rtiles != 1 || is->k != hp.cand.n) return ECG_EINVAL;
-    h.invlead = is->d_tabs;
+    h.invlead = t.extra(0).d_tabs;
     h.targets = d_targets;
     h.target = target;
     h.any = any ? 1 : 0;
     if (const hipError_t e = launch_heal(h, mode, vec_ok, st); e != hipSuccess) return hip_fail(e, "launch_heal");
-    eng.note_launch(*t.chk, st);
-    eng.note_launch(*t.ratio, st);
-    eng.note_launch(*is, st);
+    t.note_launch(st);
     return ECG_OK;
 }
 
@@ -108,13 +79,9 @@ int run_strided_heal(int n, int r, const int* H, const int* src_ids, void* d_bas
     if (!d_targets)
         if (const int rc = check_any(hp.cand); rc != ECG_OK) return rc;
     if (S == 0 || B == 0) return ECG_OK;
-    const bool vec_ok = aligned16(d_base) && sstride % 16 == 0 && bstride % 16 == 0;
-    return run_heal(hp, GF_MODE_STRIDED, B, S, d_stripe_ids, d_targets, -1, d_targets == nullptr, d_report, vec_ok, st,
-                    [&](GfLaunch& g) {
-                        g.in_base = (const uint8_t*)d_base;
-                        g.in_sstride = sstride;
-                        g.in_bstride = bstride;
-                    });
+    const StridedSrc src{d_base, sstride, bstride};
+    return run_heal(hp, GF_MODE_STRIDED, B, S, d_stripe_ids, d_targets, -1, d_targets == nullptr, d_report,
+                    src.vec_ok(), st, src);
 }
 
 }  // namespace
@@ -125,7 +92,7 @@ int ecg_heal_matrix_batch(int n, int r, const int* H, const int* src_ids, void* 
                           long long bstride, long long B, const int* d_stripe_ids, const int* d_targets, int S_sel,
                           unsigned* d_report, void* stream) {
     if (n < 1 || r < 1 || bad_sizes(B, S_sel) || !H || !src_ids || !d_base || !d_report) return ECG_EINVAL;
-    if (r > kMaxMT || n > kInlineSrc) return too_large(n, r);
+    if (const int rc = too_large(n, r); rc != ECG_OK) return rc;
     return run_strided_heal(n, r, H, src_ids, d_base, sstride, bstride, B, d_stripe_ids, d_targets, S_sel, d_report,
                             (hipStream_t)stream);
 }
@@ -134,7 +101,7 @@ int ecg_heal_encode_batch(int k, int m, const int* matrix, void* d_stripes, long
                           long long B, const int* d_stripe_ids, const int* d_targets, int S_sel, unsigned* d_report,
                           void* stream) {
     if (k < 1 || m < 1 || bad_sizes(B, S_sel) || !matrix || !d_stripes || !d_report) return ECG_EINVAL;
-    if (m > kMaxMT || k > kInlineSrc - m) return too_large((long long)k + m, m);
+    if (const int rc = too_large((long long)k + m, m); rc != ECG_OK) return rc;
     const std::vector<int> H = encode_check(k, m, matrix), ids = iota(k + m);
     return run_strided_heal(k + m, m, H.data(), ids.data(), d_stripes, sstride, bstride, B, d_stripe_ids, d_targets,
                             S_sel, d_report, (hipStream_t)stream);
@@ -158,22 +125,16 @@ int ecg_heal_ec(ecg_ec* ec, char** d_data_ptrs, char** d_coding_ptrs, int block_
     std::vector<int> H;
     int n, r;
     if (const int rc = ec_check(ec, too_large, H, n, r); rc != ECG_OK) return rc;
-    const int k = ec->impl->k;
     if (target < -1 || target >= n) return ECG_EINVAL;
-    for (int b = 0; b < n; b++)
-        if (!(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k])) return ECG_EINVAL;
+    const BlockPtrs src{ec->impl->k, n, d_data_ptrs, d_coding_ptrs};
+    if (src.any_null()) return ECG_EINVAL;
     const std::vector<int> ids = iota(n);
     const HealPlan hp = make_heal_plan(n, r, H.data(), ids.data(), false);
     if (target < 0)
         if (const int rc = check_any(hp.cand); rc != ECG_OK) return rc;
     if (block_size == 0) return ECG_OK;
-    bool vec_ok = true;
-    for (int b = 0; b < n; b++) vec_ok &= aligned16(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k]);
-    return run_heal(hp, GF_MODE_INLINE, block_size, 1, nullptr, nullptr, target, target < 0, d_report, vec_ok,
-                    ec->impl->stream, [&](GfLaunch& g) {
-                        for (int b = 0; b < n; b++)
-                            g.isrc[b] = (const uint8_t*)(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k]);
-                    });
+    return run_heal(hp, GF_MODE_INLINE, block_size, 1, nullptr, nullptr, target, target < 0, d_report, src.vec_ok(),
+                    ec->impl->stream, src);
 }
 
 int ecg_heal_counters(long long* launches, long long* bytes) {

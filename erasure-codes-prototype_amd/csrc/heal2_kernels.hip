@@ -38,17 +38,6 @@ namespace ecg {
 
 namespace {
 
-// 0x80 bits -> 0xff bytes
-__device__ __forceinline__ uint32_t byte_mask(uint32_t m) { return (m >> 7) * 0xffu; }
-
-// Block b, to be written: a table column, or -- the last R blocks of an [C | I] check, which the tables do not hold --
-// the stored block of check row b - k.  b is uniform.
-template <int MODE>
-__device__ __forceinline__ uint8_t* block_ptr(const LocateLaunch& sa, const uint8_t* sbase, int b) {
-    const uint8_t* p = b < sa.g.k ? col_ptr<MODE>(sa.g, sbase, b) : ident_ptr<MODE>(sa, sbase, b - sa.g.k);
-    return const_cast<uint8_t*>(p);
-}
-
 // The stripe's family, uniform per workgroup: singles over [0, nb) and the pairs that hold `tgt` (tgt < 0: every pair;
 // nb == 0: none).
 __device__ __forceinline__ void family(const Heal2Launch& ha, int s, int& nb, int& tgt) {
@@ -273,34 +262,13 @@ __global__ void __launch_bounds__(kThreads) gf_heal2_byte_kernel(const Heal2Laun
 // ---------------------------------------------------------------------------------------------
 // Dispatch
 
-using Launcher = hipError_t (*)(const Heal2Launch&, dim3, hipStream_t);
-
-template <int R, int MODE, bool BYTE>
-hipError_t launch_one(const Heal2Launch& a, dim3 g, hipStream_t st) {
-    void* argv[] = {(void*)&a};
-    if constexpr (BYTE)
-        return hipLaunchKernel((const void*)gf_heal2_byte_kernel<R, MODE>, g, dim3(kThreads), argv, 0, st);
-    else
-        return hipLaunchKernel((const void*)gf_heal2_kernel<R, MODE>, g, dim3(kThreads), argv, 0, st);
-}
-
-template <int MODE, bool BYTE>
-Launcher pick_r(int R) {  // R = 3 .. 8
-    if (R > kMaxMT) return nullptr;
-    return pick_of8<kHeal2MinR, Launcher>(R, nullptr,
-                                          [](auto r) -> Launcher {
-                                              constexpr int RR = decltype(r)::value;
-                                              if constexpr (RR <= kMaxMT) return launch_one<RR, MODE, BYTE>;
-                                              else return nullptr;
-                                          });
-}
-
-template <bool BYTE>
-Launcher pick(int R, int mode) {
-    if (mode == GF_MODE_INLINE) return pick_r<GF_MODE_INLINE, BYTE>(R);
-    if (mode == GF_MODE_STRIDED) return pick_r<GF_MODE_STRIDED, BYTE>(R);
-    return nullptr;
-}
+struct Heal2Kernels {  // check_launch.hpp candidate_kernel
+    template <int R, int MODE, bool BYTE>
+    static const void* kernel() {
+        if constexpr (BYTE) return (const void*)gf_heal2_byte_kernel<R, MODE>;
+        else return (const void*)gf_heal2_kernel<R, MODE>;
+    }
+};
 
 CheckLaunchLog g_heal2_log;
 
@@ -325,22 +293,10 @@ hipError_t launch_heal2(const Heal2Launch& base, int mode, bool vec_ok, hipStrea
     GfLaunch& a = ha.l.g;
     a.row_split = 0;
     a.prog_of_stripe = nullptr;
-    const long long vec_bytes = vec_ok ? (a.B & ~15LL) : 0;
-    g_heal2_log.count((vec_bytes > 0) + (vec_bytes < a.B), (long long)a.S * a.B * bl.n);
-    long long gx = 0;
-    if (vec_bytes > 0) {
-        if (const hipError_t e = plan_vector_path(a, vec_bytes, g_heal2_log, gx); e != hipSuccess) return e;
-        Launcher l = pick<false>(a.m, mode);
-        if (!l) return hipErrorInvalidValue;
-        if (const hipError_t e = l(ha, dim3((unsigned)gx), st); e != hipSuccess) return e;
-    }
-    if (vec_bytes < a.B) {
-        if (const hipError_t e = plan_byte_path(a, vec_bytes, gx); e != hipSuccess) return e;
-        Launcher l = pick<true>(a.m, mode);
-        if (!l) return hipErrorInvalidValue;
-        if (const hipError_t e = l(ha, dim3((unsigned)gx), st); e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_paths(
+        a, vec_ok, g_heal2_log, (long long)a.S * a.B * bl.n, 1,
+        [&](dim3 g) { return launch_kernel(candidate_kernel<Heal2Kernels, kHeal2MinR, false>(a.m, mode), ha, g, st); },
+        [&](dim3 g) { return launch_kernel(candidate_kernel<Heal2Kernels, kHeal2MinR, true>(a.m, mode), ha, g, st); });
 }
 
 }  // namespace ecg

@@ -31,23 +31,19 @@ int run_locate(const Plan& pl, int mode, long long B, int S, const int* d_stripe
                hipStream_t st, Fill fill) {
     LocateLaunch a;
     CandidateTables t;
-    if (const int rc = prepare_launch(pl, B, S, d_stripe_ids, d_votes, "hipMemsetAsync(locate votes)", st, fill, a, t);
+    if (const int rc = prepare_launch(pl, {}, pl.n + 2, B, S, d_stripe_ids, d_votes, "hipMemsetAsync(locate votes)", st,
+                                      fill, a, t);
         rc != ECG_OK)
         return rc;
     if (const hipError_t e = launch_locate(a, mode, vec_ok, st); e != hipSuccess) return hip_fail(e, "launch_locate");
-    Engine::instance().note_launch(*t.chk, st);
-    Engine::instance().note_launch(*t.ratio, st);
+    t.note_launch(st);
     return ECG_OK;
 }
 
 int run_strided_locate(const Plan& pl, const void* d_base, long long sstride, long long bstride, long long B,
                        const int* d_stripe_ids, int S, unsigned* d_votes, hipStream_t st) {
-    const bool vec_ok = aligned16(d_base) && sstride % 16 == 0 && bstride % 16 == 0;
-    return run_locate(pl, GF_MODE_STRIDED, B, S, d_stripe_ids, d_votes, vec_ok, st, [&](GfLaunch& g) {
-        g.in_base = (const uint8_t*)d_base;
-        g.in_sstride = sstride;
-        g.in_bstride = bstride;
-    });
+    const StridedSrc src{d_base, sstride, bstride};
+    return run_locate(pl, GF_MODE_STRIDED, B, S, d_stripe_ids, d_votes, src.vec_ok(), st, src);
 }
 
 }  // namespace
@@ -58,7 +54,7 @@ int ecg_locate_matrix_batch(int n, int r, const int* H, const int* src_ids, cons
                             long long bstride, long long B, const int* d_stripe_ids, int S_sel, unsigned* d_votes,
                             void* stream) {
     if (n < 1 || r < 1 || bad_sizes(B, S_sel) || !H || !src_ids || !d_base || !d_votes) return ECG_EINVAL;
-    if (r > kMaxMT || n > kInlineSrc) return too_large(n, r);
+    if (const int rc = too_large(n, r); rc != ECG_OK) return rc;
     if (S_sel == 0 || B == 0) return ECG_OK;
     return run_strided_locate(make_plan(n, r, H, src_ids, true), d_base, sstride, bstride, B, d_stripe_ids, S_sel,
                               d_votes, (hipStream_t)stream);
@@ -68,7 +64,7 @@ int ecg_locate_encode_batch(int k, int m, const int* matrix, const void* d_strip
                             long long bstride, long long B, const int* d_stripe_ids, int S_sel, unsigned* d_votes,
                             void* stream) {
     if (k < 1 || m < 1 || bad_sizes(B, S_sel) || !matrix || !d_stripes || !d_votes) return ECG_EINVAL;
-    if (m > kMaxMT || k > kInlineSrc - m) return too_large((long long)k + m, m);
+    if (const int rc = too_large((long long)k + m, m); rc != ECG_OK) return rc;
     if (S_sel == 0 || B == 0) return ECG_OK;
     const std::vector<int> H = encode_check(k, m, matrix), ids = iota(k + m);
     return run_strided_locate(make_plan(k + m, m, H.data(), ids.data(), true), d_stripes, sstride, bstride, B,
@@ -93,18 +89,12 @@ int ecg_locate_ec(ecg_ec* ec, char** d_data_ptrs, char** d_coding_ptrs, int bloc
     std::vector<int> H;
     int n, r;
     if (const int rc = ec_check(ec, too_large, H, n, r); rc != ECG_OK) return rc;
-    const int k = ec->impl->k;
-    for (int b = 0; b < n; b++)
-        if (!(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k])) return ECG_EINVAL;
+    const BlockPtrs src{ec->impl->k, n, d_data_ptrs, d_coding_ptrs};
+    if (src.any_null()) return ECG_EINVAL;
     if (block_size == 0) return ECG_OK;
-    bool vec_ok = true;
-    for (int b = 0; b < n; b++) vec_ok &= aligned16(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k]);
     const std::vector<int> ids = iota(n);
     return run_locate(make_plan(n, r, H.data(), ids.data(), false), GF_MODE_INLINE, block_size, 1, nullptr, d_votes,
-                      vec_ok, ec->impl->stream, [&](GfLaunch& g) {
-                          for (int b = 0; b < n; b++)
-                              g.isrc[b] = (const uint8_t*)(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k]);
-                      });
+                      src.vec_ok(), ec->impl->stream, src);
 }
 
 int ecg_locate_verdict(int n, const unsigned* h_votes, int* ids, int cap, int* n_ids) {

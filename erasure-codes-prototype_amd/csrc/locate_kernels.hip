@@ -94,28 +94,13 @@ __global__ void __launch_bounds__(kThreads) gf_locate_byte_kernel(const LocateLa
 // ---------------------------------------------------------------------------------------------
 // Dispatch
 
-using Launcher = hipError_t (*)(const LocateLaunch&, dim3, hipStream_t);
-
-template <int R, int MODE, bool BYTE>
-hipError_t launch_one(const LocateLaunch& a, dim3 g, hipStream_t st) {
-    void* argv[] = {(void*)&a};
-    if constexpr (BYTE)
-        return hipLaunchKernel((const void*)gf_locate_byte_kernel<R, MODE>, g, dim3(kThreads), argv, 0, st);
-    else
-        return hipLaunchKernel((const void*)gf_locate_kernel<R, MODE>, g, dim3(kThreads), argv, 0, st);
-}
-
-template <int MODE, bool BYTE>
-Launcher pick_r(int R) {
-    return pick_of8<1, Launcher>(R, nullptr, [](auto r) { return launch_one<decltype(r)::value, MODE, BYTE>; });
-}
-
-template <bool BYTE>
-Launcher pick(int R, int mode) {
-    if (mode == GF_MODE_INLINE) return pick_r<GF_MODE_INLINE, BYTE>(R);
-    if (mode == GF_MODE_STRIDED) return pick_r<GF_MODE_STRIDED, BYTE>(R);
-    return nullptr;
-}
+struct LocateKernels {  // check_launch.hpp candidate_kernel
+    template <int R, int MODE, bool BYTE>
+    static const void* kernel() {
+        if constexpr (BYTE) return (const void*)gf_locate_byte_kernel<R, MODE>;
+        else return (const void*)gf_locate_kernel<R, MODE>;
+    }
+};
 
 CheckLaunchLog g_locate_log;
 
@@ -137,22 +122,10 @@ hipError_t launch_locate(const LocateLaunch& base, int mode, bool vec_ok, hipStr
     GfLaunch& a = sa.g;
     a.row_split = 0;
     a.prog_of_stripe = nullptr;
-    const long long vec_bytes = vec_ok ? (a.B & ~15LL) : 0;
-    g_locate_log.count((vec_bytes > 0) + (vec_bytes < a.B), (long long)a.S * a.B * sa.n);
-    long long gx = 0;
-    if (vec_bytes > 0) {
-        if (const hipError_t e = plan_vector_path(a, vec_bytes, g_locate_log, gx); e != hipSuccess) return e;
-        Launcher l = pick<false>(a.m, mode);
-        if (!l) return hipErrorInvalidValue;
-        if (const hipError_t e = l(sa, dim3((unsigned)gx), st); e != hipSuccess) return e;
-    }
-    if (vec_bytes < a.B) {
-        if (const hipError_t e = plan_byte_path(a, vec_bytes, gx); e != hipSuccess) return e;
-        Launcher l = pick<true>(a.m, mode);
-        if (!l) return hipErrorInvalidValue;
-        if (const hipError_t e = l(sa, dim3((unsigned)gx), st); e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_paths(
+        a, vec_ok, g_locate_log, (long long)a.S * a.B * sa.n, 1,
+        [&](dim3 g) { return launch_kernel(candidate_kernel<LocateKernels, 1, false>(a.m, mode), sa, g, st); },
+        [&](dim3 g) { return launch_kernel(candidate_kernel<LocateKernels, 1, true>(a.m, mode), sa, g, st); });
 }
 
 }  // namespace ecg

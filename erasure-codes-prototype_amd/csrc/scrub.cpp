@@ -53,13 +53,13 @@ int run_check(const Check& chk, int mode, long long B, int S, unsigned* d_counts
 
 int run_strided_check(const Check& chk, const void* d_base, long long sstride, long long bstride, long long B, int S,
                       unsigned* d_counts, hipStream_t st) {
-    const bool vec_ok = aligned16(d_base) && sstride % 16 == 0 && bstride % 16 == 0;
-    return run_check(chk, GF_MODE_STRIDED, B, S, d_counts, vec_ok, st, [&](GfLaunch& g) {
-        g.in_base = (const uint8_t*)d_base;
-        g.in_sstride = sstride;
-        g.in_bstride = bstride;
-    });
+    const StridedSrc src{d_base, sstride, bstride};
+    return run_check(chk, GF_MODE_STRIDED, B, S, d_counts, src.vec_ok(), st, src);
 }
+
+// The scrub has a kernel for every r (row tiles); only the inline form's descriptor bounds n.
+int any_size(int, int) { return ECG_OK; }
+int inline_size(int n, int) { return n > kInlineSrc ? ECG_EINVAL : ECG_OK; }
 
 }  // namespace
 
@@ -86,11 +86,9 @@ int ecg_scrub_ec_batch(ecg_ec* ec, const void* d_stripes, long long sstride, lon
                        unsigned* d_counts, void* stream) {
     if (!ec || bad_sizes(B, S) || !d_stripes || !d_counts || ec->impl->mem != ECG_MEM_DEVICE) return ECG_EINVAL;
     std::vector<int> H;
-    const int r = ec->impl->check_matrix(H);
-    if (r < 0) return r;
-    if (r < 1) return ECG_EINVAL;
+    int n, r;
+    if (const int rc = ec_check(ec, any_size, H, n, r); rc != ECG_OK) return rc;
     if (S == 0 || B == 0) return ECG_OK;
-    const int n = (int)(H.size() / (size_t)r);
     const std::vector<int> ids = iota(n);
     return run_strided_check(make_check(n, r, H.data(), ids.data(), true), d_stripes, sstride, bstride, B, S, d_counts,
                              (hipStream_t)stream);
@@ -100,22 +98,14 @@ int ecg_scrub_ec(ecg_ec* ec, char** d_data_ptrs, char** d_coding_ptrs, int block
     if (!ec || block_size < 0 || !d_data_ptrs || !d_coding_ptrs || !d_counts || ec->impl->mem != ECG_MEM_DEVICE)
         return ECG_EINVAL;
     std::vector<int> H;
-    const int r = ec->impl->check_matrix(H);
-    if (r < 0) return r;
-    if (r < 1) return ECG_EINVAL;
-    const int k = ec->impl->k, n = (int)(H.size() / (size_t)r);
-    if (n > kInlineSrc) return ECG_EINVAL;
-    for (int b = 0; b < n; b++)
-        if (!(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k])) return ECG_EINVAL;
+    int n, r;
+    if (const int rc = ec_check(ec, inline_size, H, n, r); rc != ECG_OK) return rc;
+    const BlockPtrs src{ec->impl->k, n, d_data_ptrs, d_coding_ptrs};
+    if (src.any_null()) return ECG_EINVAL;
     if (block_size == 0) return ECG_OK;
-    bool vec_ok = true;
-    for (int b = 0; b < n; b++) vec_ok &= aligned16(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k]);
     const std::vector<int> ids = iota(n);
-    return run_check(make_check(n, r, H.data(), ids.data(), false), GF_MODE_INLINE, block_size, 1, d_counts, vec_ok,
-                     ec->impl->stream, [&](GfLaunch& g) {
-                         for (int b = 0; b < n; b++)
-                             g.isrc[b] = (const uint8_t*)(b < k ? d_data_ptrs[b] : d_coding_ptrs[b - k]);
-                     });
+    return run_check(make_check(n, r, H.data(), ids.data(), false), GF_MODE_INLINE, block_size, 1, d_counts,
+                     src.vec_ok(), ec->impl->stream, src);
 }
 
 int ecg_scrub_suspects(int r, int n, const int* H, const unsigned* h_counts, int* ids, int cap) {

@@ -164,33 +164,19 @@ __global__ void __launch_bounds__(kThreads) gf_scrub_byte_kernel(const ScrubLaun
 // ---------------------------------------------------------------------------------------------
 // Dispatch
 
-using Launcher = hipError_t (*)(const ScrubLaunch&, dim3, hipStream_t);
-
-template <int MT, int MODE, bool BIN>
-hipError_t vec_launch(const ScrubLaunch& a, dim3 g, hipStream_t st) {
-    void* argv[] = {(void*)&a};
-    return hipLaunchKernel((const void*)gf_scrub_kernel<MT, MODE, BIN>, g, dim3(kThreads), argv, 0, st);
-}
-
-template <int MT, int MODE, bool BIN>
-hipError_t byte_launch(const ScrubLaunch& a, dim3 g, hipStream_t st) {
-    void* argv[] = {(void*)&a};
-    return hipLaunchKernel((const void*)gf_scrub_byte_kernel<MT, MODE, BIN>, g, dim3(kThreads), argv, 0, st);
-}
-
 template <int MODE, bool BIN, bool BYTE>
-Launcher pick_mt(int MT) {
-    const auto one = [](auto mt) -> Launcher {
-        if constexpr (BYTE) return byte_launch<decltype(mt)::value, MODE, BIN>;
-        else return vec_launch<decltype(mt)::value, MODE, BIN>;
+const void* pick_mt(int MT) {
+    const auto one = [](auto mt) -> const void* {
+        if constexpr (BYTE) return (const void*)gf_scrub_byte_kernel<decltype(mt)::value, MODE, BIN>;
+        else return (const void*)gf_scrub_kernel<decltype(mt)::value, MODE, BIN>;
     };
     if constexpr (BIN)  // wide BINARY tiles (kMaxMTBin)
-        if (MT > 8) return pick_of8<9, Launcher>(MT, nullptr, one);
-    return pick_of8<1, Launcher>(MT, nullptr, one);
+        if (MT > 8) return pick_of8<9, const void*>(MT, nullptr, one);
+    return pick_of8<1, const void*>(MT, nullptr, one);
 }
 
 template <bool BYTE>
-Launcher pick(const GfLaunch& a, int mode) {
+const void* pick(const GfLaunch& a, int mode) {
     if (mode == GF_MODE_INLINE)
         return a.binary ? pick_mt<GF_MODE_INLINE, true, BYTE>(a.MT) : pick_mt<GF_MODE_INLINE, false, BYTE>(a.MT);
     if (mode == GF_MODE_STRIDED)
@@ -217,23 +203,10 @@ hipError_t launch_scrub(const ScrubLaunch& base, int mode, bool vec_ok, hipStrea
     ScrubLaunch sa = base;
     GfLaunch& a = sa.g;
     a.row_split = 0;
-    const long long vec_bytes = vec_ok ? (a.B & ~15LL) : 0;
-    g_scrub_log.count((vec_bytes > 0) + (vec_bytes < a.B),
-                      (long long)a.S * a.B * ((long long)a.rtiles * a.k + (sa.ident ? a.m : 0)));
-    long long gx = 0;
-    if (vec_bytes > 0) {
-        if (const hipError_t e = plan_vector_path(a, vec_bytes, g_scrub_log, gx); e != hipSuccess) return e;
-        Launcher l = pick<false>(a, mode);
-        if (!l) return hipErrorInvalidValue;
-        if (const hipError_t e = l(sa, dim3((unsigned)gx, (unsigned)a.rtiles), st); e != hipSuccess) return e;
-    }
-    if (vec_bytes < a.B) {
-        if (const hipError_t e = plan_byte_path(a, vec_bytes, gx); e != hipSuccess) return e;
-        Launcher l = pick<true>(a, mode);
-        if (!l) return hipErrorInvalidValue;
-        if (const hipError_t e = l(sa, dim3((unsigned)gx, (unsigned)a.rtiles), st); e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_paths(
+        a, vec_ok, g_scrub_log, (long long)a.S * a.B * ((long long)a.rtiles * a.k + (sa.ident ? a.m : 0)), a.rtiles,
+        [&](dim3 g) { return launch_kernel(pick<false>(a, mode), sa, g, st); },
+        [&](dim3 g) { return launch_kernel(pick<true>(a, mode), sa, g, st); });
 }
 
 }  // namespace ecg

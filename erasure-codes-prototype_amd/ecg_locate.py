@@ -17,14 +17,15 @@ There is no CPU fallback: if libecg_locate.so is missing or has no GPU to run on
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 
+import _ecg_checklib as _checklib
 import ecg
+from _ecg_checklib import I, IP, LL, LLP, P, PP, UP, LAST_LAUNCH_FIELDS  # LAST_LAUNCH_FIELDS: re-exported
 from ecg import EcgError, _check, _ints, _ptrs, _stream, _strides, torch
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(ecg.LIB_PATH)), "libecg_locate.so")
+LIB_PATH = _checklib.lib_path("ecg_locate")
 
 # Every symbol include/ecg_locate.h declares (checked by tests/test_locate_host.py).
 EXPORTS = [
@@ -35,57 +36,36 @@ EXPORTS = [
 # ecg_locate_verdict statuses (a value >= 0 is a block id)
 CLEAN, AMBIGUOUS, MULTIPLE = -100, -101, -102
 
+_SIG = {
+    "ecg_locate_matrix_batch": ([I, I, IP, IP, P, LL, LL, LL, P, I, P, P], I),
+    "ecg_locate_encode_batch": ([I, I, IP, P, LL, LL, LL, P, I, P, P], I),
+    "ecg_locate_ec_batch": ([P, P, LL, LL, LL, P, I, P, P], I),
+    "ecg_locate_ec": ([P, PP, PP, I, P], I),
+    "ecg_locate_verdict": ([I, UP, IP, I, IP], I),
+    "ecg_locate_counters": ([LLP] * 2, I),
+    "ecg_locate_last_launch": ([IP, I], I),
+}
+
 _L = None
 
 
 def lib():
     """Load libecg_locate.so (after libecg.so, which it links against)."""
     global _L
-    if _L is not None:
-        return _L
-    ecg.lib()
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} not built (run `make -C erasure-codes-prototype_amd`)")
-    L = ctypes.CDLL(LIB_PATH)
-    I, LL, P = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p
-    IP = ctypes.POINTER(ctypes.c_int)
-    UP = ctypes.POINTER(ctypes.c_uint)
-    PP = ctypes.POINTER(ctypes.c_void_p)
-    sig = {
-        "ecg_locate_matrix_batch": ([I, I, IP, IP, P, LL, LL, LL, P, I, P, P], I),
-        "ecg_locate_encode_batch": ([I, I, IP, P, LL, LL, LL, P, I, P, P], I),
-        "ecg_locate_ec_batch": ([P, P, LL, LL, LL, P, I, P, P], I),
-        "ecg_locate_ec": ([P, PP, PP, I, P], I),
-        "ecg_locate_verdict": ([I, UP, IP, I, IP], I),
-        "ecg_locate_counters": ([ctypes.POINTER(LL)] * 2, I),
-        "ecg_locate_last_launch": ([IP, I], I),
-    }
-    for name, (args, res) in sig.items():
-        f = getattr(L, name)
-        f.argtypes = args
-        f.restype = res
-    _L = L
-    return L
+    if _L is None:
+        _L = _checklib.load(LIB_PATH, _SIG)
+    return _L
 
 
 def _selection(stripe_ids, S):
     """(device pointer or None, S_sel) of a stripe selection: None = all S stripes in order."""
-    if stripe_ids is None:
-        return None, S
-    if (stripe_ids.dtype != torch.int32 or not stripe_ids.is_cuda or stripe_ids.dim() != 1 or
-            not stripe_ids.is_contiguous()):
-        raise EcgError(ecg.ECG_EINVAL, "locate: stripe_ids must be a contiguous 1-D int32 CUDA tensor")
-    return stripe_ids.data_ptr(), int(stripe_ids.numel())
+    ids, _, S_sel = _checklib.selection("locate", stripe_ids, None, S)
+    return ids, S_sel
 
 
 def _votes(out, S_sel, n, device):
     """The (S_sel, n + 2) int32 result tensor: `out` if given (checked), else a fresh one.  The call zeroes it."""
-    if out is None:
-        return torch.empty((S_sel, n + 2), dtype=torch.int32, device=device)
-    if (tuple(out.shape) != (S_sel, n + 2) or out.dtype != torch.int32 or not out.is_cuda or
-            not out.is_contiguous()):
-        raise EcgError(ecg.ECG_EINVAL, "locate: out must be a contiguous int32 CUDA tensor of shape (S_sel, n + 2)")
-    return out
+    return _checklib.result_tensor("locate", out, (S_sel, n + 2), device, "(S_sel, n + 2)")
 
 
 def matrix_batch(H, src_ids, stripes, stripe_ids=None, out=None, stream=None):
@@ -158,21 +138,11 @@ def verdict(votes_row):
 
 def counters():
     """Process-wide {launches, bytes}: locate kernels launched and the bytes they read as planned (S_sel * B * n)."""
-    v = [ctypes.c_longlong(0) for _ in range(2)]
-    _check(lib().ecg_locate_counters(*[ctypes.byref(x) for x in v]), "locate.counters")
-    return {"launches": v[0].value, "bytes": v[1].value}
-
-
-LAST_LAUNCH_FIELDS = ("grid_map", "map_group", "cols_per_wg", "wg_per_stripe", "S", "rtiles")
+    return _checklib.counters(lib(), "locate")
 
 
 def last_launch():
     """Geometry of the process's most recent vector-path locate launch, as placed in the launch descriptor after the
     fallbacks (include/ecg_locate.h ecg_locate_last_launch): {grid_map, map_group, cols_per_wg, wg_per_stripe, S,
     rtiles}, all zero before the first.  Byte-kernel launches do not change it."""
-    n = lib().ecg_locate_last_launch(None, 0)
-    if n != len(LAST_LAUNCH_FIELDS):
-        raise EcgError(ecg.ECG_EINVAL, f"locate.last_launch: library has {n} fields")
-    v = (ctypes.c_int * n)()
-    lib().ecg_locate_last_launch(v, n)
-    return dict(zip(LAST_LAUNCH_FIELDS, (int(x) for x in v)))
+    return _checklib.last_launch(lib(), "locate")

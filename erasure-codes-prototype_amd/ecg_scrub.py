@@ -12,14 +12,15 @@ There is no CPU fallback: if libecg_scrub.so is missing or has no GPU to run on,
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 
+import _ecg_checklib as _checklib
 import ecg
-from ecg import EcgError, _check, _ints, _ptrs, _stream, _strides, torch
+from _ecg_checklib import I, IP, LL, LLP, P, PP, UP, LAST_LAUNCH_FIELDS  # LAST_LAUNCH_FIELDS: re-exported
+from ecg import _check, _ints, _ptrs, _stream, _strides, torch
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(ecg.LIB_PATH)), "libecg_scrub.so")
+LIB_PATH = _checklib.lib_path("ecg_scrub")
 
 # Every symbol include/ecg_scrub.h declares (checked by tests/test_scrub_host.py).
 EXPORTS = [
@@ -27,46 +28,30 @@ EXPORTS = [
     "ecg_scrub_counters", "ecg_scrub_last_launch",
 ]
 
+_SIG = {
+    "ecg_scrub_matrix_batch": ([I, I, IP, IP, P, LL, LL, LL, I, P, P], I),
+    "ecg_scrub_encode_batch": ([I, I, IP, P, LL, LL, LL, I, P, P], I),
+    "ecg_scrub_ec_batch": ([P, P, LL, LL, LL, I, P, P], I),
+    "ecg_scrub_ec": ([P, PP, PP, I, P], I),
+    "ecg_scrub_suspects": ([I, I, IP, UP, IP, I], I),
+    "ecg_scrub_counters": ([LLP] * 2, I),
+    "ecg_scrub_last_launch": ([IP, I], I),
+}
+
 _L = None
 
 
 def lib():
     """Load libecg_scrub.so (after libecg.so, which it links against)."""
     global _L
-    if _L is not None:
-        return _L
-    ecg.lib()
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} not built (run `make -C erasure-codes-prototype_amd`)")
-    L = ctypes.CDLL(LIB_PATH)
-    I, LL, P = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p
-    IP = ctypes.POINTER(ctypes.c_int)
-    UP = ctypes.POINTER(ctypes.c_uint)
-    PP = ctypes.POINTER(ctypes.c_void_p)
-    sig = {
-        "ecg_scrub_matrix_batch": ([I, I, IP, IP, P, LL, LL, LL, I, P, P], I),
-        "ecg_scrub_encode_batch": ([I, I, IP, P, LL, LL, LL, I, P, P], I),
-        "ecg_scrub_ec_batch": ([P, P, LL, LL, LL, I, P, P], I),
-        "ecg_scrub_ec": ([P, PP, PP, I, P], I),
-        "ecg_scrub_suspects": ([I, I, IP, UP, IP, I], I),
-        "ecg_scrub_counters": ([ctypes.POINTER(LL)] * 2, I),
-        "ecg_scrub_last_launch": ([IP, I], I),
-    }
-    for name, (args, res) in sig.items():
-        f = getattr(L, name)
-        f.argtypes = args
-        f.restype = res
-    _L = L
-    return L
+    if _L is None:
+        _L = _checklib.load(LIB_PATH, _SIG)
+    return _L
 
 
 def _counts(out, S, r, device):
     """The (S, r) int32 result tensor: `out` if given (checked), else a fresh one.  The call zeroes it."""
-    if out is None:
-        return torch.empty((S, r), dtype=torch.int32, device=device)
-    if (tuple(out.shape) != (S, r) or out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous()):
-        raise EcgError(ecg.ECG_EINVAL, "scrub: out must be a contiguous int32 CUDA tensor of shape (S, r)")
-    return out
+    return _checklib.result_tensor("scrub", out, (S, r), device, "(S, r)")
 
 
 def matrix_batch(H, src_ids, stripes, out=None, stream=None):
@@ -131,21 +116,11 @@ def suspects(H, counts):
 def counters():
     """Process-wide {launches, bytes}: scrub kernels launched and the bytes they read as planned (S * B * k_in per
     row tile)."""
-    v = [ctypes.c_longlong(0) for _ in range(2)]
-    _check(lib().ecg_scrub_counters(*[ctypes.byref(x) for x in v]), "scrub.counters")
-    return {"launches": v[0].value, "bytes": v[1].value}
-
-
-LAST_LAUNCH_FIELDS = ("grid_map", "map_group", "cols_per_wg", "wg_per_stripe", "S", "rtiles")
+    return _checklib.counters(lib(), "scrub")
 
 
 def last_launch():
     """Geometry of the process's most recent vector-path scrub launch, as placed in the launch descriptor after the
     fallbacks (include/ecg_scrub.h ecg_scrub_last_launch): {grid_map, map_group, cols_per_wg, wg_per_stripe, S,
     rtiles}, all zero before the first.  Byte-kernel launches do not change it."""
-    n = lib().ecg_scrub_last_launch(None, 0)
-    if n != len(LAST_LAUNCH_FIELDS):
-        raise EcgError(ecg.ECG_EINVAL, f"scrub.last_launch: library has {n} fields")
-    v = (ctypes.c_int * n)()
-    lib().ecg_scrub_last_launch(v, n)
-    return dict(zip(LAST_LAUNCH_FIELDS, (int(x) for x in v)))
+    return _checklib.last_launch(lib(), "scrub")

@@ -430,6 +430,31 @@ def test_idempotence_and_report_overwritten(torch_cuda, heal):
 
 
 @gpu
+def test_prefilled_out_is_zeroed_before_the_kernels(torch_cuda, heal):
+    """RS(6,4), S = 2, B = 48 + 5 (a vector and a byte launch): the report written into an `out` prefilled with a
+    nonzero pattern equals the report of a call without `out` over the same damage, so the zeroing of the report still
+    precedes both kernels on the stream."""
+    torch = torch_cuda
+    B = 48 + 5
+    _, flat, _, original = _code(RS64, 2, B, 80)
+    stripes = original.copy()
+    stripes[0, 1, 3] ^= 0x5A
+    stripes[0, 7, 20:40] ^= 0x11
+    stripes[1, 0, 46:50] ^= 0x07                                         # across the end of the vector path
+    stripes[1, 9, B - 2:] ^= 0x33
+    g, want, (img, d, view) = _encode_case(torch, heal, RS64, stripes, original=original)
+    assert g[0, 1] == 1 and g[0, 7] == 20 and g[1, 0] == 4 and g[1, 9] == 2
+    d.copy_(torch.from_numpy(img).to(d.device))                          # damaged again
+    out = torch.full((2, 12), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    c0 = heal.counters()
+    assert heal.encode_batch(6, 4, flat, view, out=out) is out
+    torch.cuda.synchronize()
+    assert heal.counters()["launches"] - c0["launches"] == 2             # the vector and the byte kernel
+    assert np.array_equal(out.cpu().numpy().astype(np.int64), g)
+    assert np.array_equal(d.cpu().numpy(), want)
+
+
+@gpu
 def test_heal_flushes_the_batch_scope(ecg, torch_cuda, heal):
     """A dev_matrix_encode recorded in a batch scope, then a heal of the same blocks inside the scope: the heal
     flushes the scope first, so it sees the encode's parity (nothing to correct), not the stale one."""
