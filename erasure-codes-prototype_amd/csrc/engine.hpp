@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/ecg.h"  // status codes ECG_*
+#include "batch_plan.hpp"       // the flush's planning types were declared here once: includers still get them
 #include "gf_kernels.hpp"
 #include "matrix.hpp"
 
@@ -234,8 +235,8 @@ private:
 //   1. composes away scratch blocks (batch_scratch): a block written and later read inside the scope
 //      whose memory the caller declared scratch is never written -- its readers take the linear map
 //      that produced it instead (the helper partial + main partial + perform_addition sequence of a
-//      partial-decoding repair becomes one region product per repair, compose_scratch below);
-//   2. groups the calls (schedule_groups below): calls with the same plan, block size, stream and
+//      partial-decoding repair becomes one region product per repair, batch_plan.hpp compose_scratch);
+//   2. groups the calls (batch_plan.hpp schedule_groups): calls with the same plan, block size, stream and
 //      device join one group unless a data dependence orders them apart, and each group goes out as
 //      ONE launch per op -- strided when its blocks form one strided batch, a pointer-table launch
 //      otherwise.  Groups launch in an order that respects every read/write dependence of the recorded
@@ -248,7 +249,7 @@ int batch_begin();
 int batch_flush();
 int batch_end();
 bool batch_active();
-// Host-tier calls of the scope are recorded too (ecg_batch_defer_host): see DeferScope::hq in engine.cpp.
+// Host-tier calls of the scope are recorded too (ecg_batch_defer_host): see DeferScope::hq in engine_internal.hpp.
 int batch_defer_host(int on);
 int record_host(Engine* eng, const std::vector<LinearOp>& ops, uint8_t* const* blocks, int nblocks, long long B);
 int host_flush();
@@ -264,155 +265,6 @@ struct FlushStats {
     long long recorded = 0, composed = 0, groups = 0, launches = 0, materialised = 0;
 };
 FlushStats last_flush_stats();
-
-// One recorded device-tier call: its plan (shared by calls with an equal plan) over its block space.
-struct DeferredCall {
-    Engine* eng;
-    hipStream_t st;
-    long long B;
-    std::shared_ptr<const std::vector<LinearOp>> ops;
-    std::vector<uint8_t*> blocks;  // device pointers
-};
-
-// Scratch ranges of a scope (merged, disjoint).  A block [p, p + B) is scratch if one range holds it.
-class ScratchRanges {
-public:
-    void add(uintptr_t lo, uintptr_t hi);
-    bool holds(const void* p, long long B) const;
-    bool empty() const { return r_.empty(); }
-    void clear() { r_.clear(); }
-
-private:
-    std::vector<std::pair<uintptr_t, uintptr_t>> r_;  // sorted by start, disjoint, [lo, hi)
-};
-
-// Scratch composition (pure host logic, no HIP; fuzzed in tests/sanitize/host_fuzz.cpp against a
-// sequential interpreter).  Walks the recorded calls in order, keeping for every scratch block written
-// so far the linear combination of real blocks it holds (an "expression").  A call reading a scratch
-// block with an expression reads that combination's blocks instead (coefficients multiplied out over
-// GF(2^8)); a call writing a scratch block only records the expression.  An expression is written for
-// real ("materialised") before any block it reads is overwritten, when a reader runs on another
-// stream / device / block size, and -- unless `scope_end` -- for every expression left at the end
-// (a mid-scope flush must leave memory as the sequential calls would).  At scope end unconsumed
-// scratch contents are undefined: that is the contract of batch_scratch.  Blocks are compared by
-// address, as in the hazard check (blocks of one scope are identical or disjoint).  Calls that touch
-// neither scratch nor an expression pass through unchanged (their plan pointer kept).
-std::vector<DeferredCall> compose_scratch(std::vector<DeferredCall>&& q, const ScratchRanges& scratch,
-                                          bool scope_end, long long* materialised);
-
-// Block addresses are often aligned to the block size (1 MiB and up): a full 64-bit mix (splitmix64's
-// finaliser) so that their low bits, which pick the slot, are not mostly zero.
-inline size_t ptr_hash(uintptr_t p) {
-    unsigned long long x = (unsigned long long)p;
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdULL;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ULL;
-    x ^= x >> 33;
-    return (size_t)x;
-}
-
-// Open-addressing map block address -> the latest group (index + 1) that read / wrote it, for the
-// flush's scheduler.  0 = never touched.
-class PtrGroups {
-public:
-    struct Slot {
-        uintptr_t p;
-        int rd, wr;
-    };
-    Slot& at(const void* ptr) {
-        if ((count_ + 1) * 2 > slots_.size()) grow();
-        const uintptr_t p = (uintptr_t)ptr;
-        for (size_t i = hash(p) & mask_;; i = (i + 1) & mask_) {
-            if (slots_[i].p == p) return slots_[i];
-            if (slots_[i].p == 0) {
-                slots_[i] = Slot{p, 0, 0};
-                count_++;
-                return slots_[i];
-            }
-        }
-    }
-    // empty, with room for n addresses without growing (the flush's scheduler reuses one per thread)
-    void reset(size_t n) {
-        size_t want = 1024;
-        while (want < 4 * n) want <<= 1;
-        if (slots_.size() < want) {
-            slots_.assign(want, Slot{0, 0, 0});
-            mask_ = want - 1;
-        } else if (count_) {
-            std::fill(slots_.begin(), slots_.end(), Slot{0, 0, 0});
-        }
-        count_ = 0;
-    }
-    int last_write(const void* ptr) const { const Slot* s = find(ptr); return s ? s->wr : 0; }
-    const Slot* find_slot(const void* ptr) const { return find(ptr); }
-    int last_touch(const void* ptr) const { const Slot* s = find(ptr); return s ? std::max(s->rd, s->wr) : 0; }
-
-private:
-    const Slot* find(const void* ptr) const {
-        if (slots_.empty()) return nullptr;
-        const uintptr_t p = (uintptr_t)ptr;
-        for (size_t i = hash(p) & mask_;; i = (i + 1) & mask_) {
-            if (slots_[i].p == p) return &slots_[i];
-            if (slots_[i].p == 0) return nullptr;
-        }
-    }
-    static size_t hash(uintptr_t p) { return ptr_hash(p); }
-    void grow() {
-        std::vector<Slot> old;
-        old.swap(slots_);
-        slots_.assign(old.empty() ? 1024 : old.size() * 2, Slot{0, 0, 0});
-        mask_ = slots_.size() - 1;
-        count_ = 0;
-        for (const Slot& s : old)
-            if (s.p) at((const void*)s.p) = s;
-    }
-    std::vector<Slot> slots_;
-    size_t mask_ = 0, count_ = 0;
-};
-
-// Grouping of the flush (pure host logic, no HIP; fuzzed against a quadratic legality check in
-// tests/sanitize/host_fuzz.cpp).  Calls [0, n) in program order; key(c) >= 0 names the call's plan
-// class (same plan or single-op shape, block size, stream, device).  Each call joins the EARLIEST group of
-// its key that comes after every group holding an earlier call it depends on (one that writes a block it
-// reads or writes, or reads a block it writes); if there is none it opens a new group at the end.
-// Launching the groups in index order, each group's calls in one launch, therefore respects every
-// dependence of the program order (two dependent calls always sit in groups i < j), and independent calls
-// of one plan -- the reference's per-stripe loop, even with several plans interleaved per stripe -- share a
-// launch.  Earliest, not latest: in a two-block repair whose second plan reads the block its first plan
-// rebuilt (handle_repair.cpp per plan), every stripe's first plan shares one group and every second plan
-// the next, instead of a new pair of groups per stripe (a launch per stripe).  A call placed before a later
-// group of its key depends on nothing in between, and calls after it see its group in `seen`.
-// reads(c, f) / writes(c, f) call f(address) per block call c reads / writes.  Returns the groups,
-// each listing its calls in program order.
-template <class Key, class Reads, class Writes>
-std::vector<std::vector<size_t>> schedule_groups(size_t n, Key key, Reads reads, Writes writes) {
-    std::vector<std::vector<size_t>> groups;
-    std::vector<std::vector<int>> of_key;  // key -> its groups' index + 1, ascending
-    thread_local PtrGroups seen;
-    seen.reset(4 * n);
-    for (size_t c = 0; c < n; c++) {
-        int lo = 0;  // the call must go into a group with index + 1 > lo
-        reads(c, [&](const void* p) { lo = std::max(lo, seen.last_write(p)); });
-        writes(c, [&](const void* p) { lo = std::max(lo, seen.last_touch(p)); });
-        const int kc = key(c);
-        if ((size_t)kc >= of_key.size()) of_key.resize((size_t)kc + 1);
-        std::vector<int>& mine = of_key[(size_t)kc];
-        const auto it = std::upper_bound(mine.begin(), mine.end(), lo);
-        int g1;
-        if (it != mine.end()) {
-            g1 = *it;
-        } else {
-            groups.emplace_back();
-            g1 = (int)groups.size();
-            mine.push_back(g1);
-        }
-        groups[(size_t)g1 - 1].push_back(c);
-        reads(c, [&](const void* p) { PtrGroups::Slot& s = seen.at(p); s.rd = std::max(s.rd, g1); });
-        writes(c, [&](const void* p) { PtrGroups::Slot& s = seen.at(p); s.wr = std::max(s.wr, g1); });
-    }
-    return groups;
-}
 
 // Resident call worker of the calling thread's device (ECG_OPT_CALL_WORKER): calls, launches, relaunches,
 // off now (set-up failure, or a cooldown after a timed-out call).

@@ -56,7 +56,7 @@ S_STRIDED = 3
 
 
 def tile(binary, m):
-    mt = min(m, K_MAX_MT_BIN if binary else K_MAX_MT)  # engine.cpp program_set: ps->MT, ps->rtiles
+    mt = min(m, K_MAX_MT_BIN if binary else K_MAX_MT)  # program_cache.cpp program_set: ps->MT, ps->rtiles
     return mt, (m + mt - 1) // mt
 
 
@@ -114,7 +114,7 @@ def expected_keys(c, M=None):
     elif c.form == "ptrs":
         mode = MODE_PTRS
     elif c.form == "host":
-        mode = MODE_INLINE_LAT  # engine.cpp run_host: launch_one(..., latency = true)
+        mode = MODE_INLINE_LAT  # host_tier.cpp run_host: launch_one(..., latency = true)
     else:  # engine.cpp launch_one: lat = B <= ECG_OPT_LAT_DWORD_BYTES && k <= kLatMaxSrc
         mode = MODE_INLINE_LAT if c.B <= c.lat and c.k <= LAT_MAX_SRC else MODE_INLINE
     keys = {}

@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "ecg.h"
-#include "engine.hpp"  // ecg::schedule_groups, ecg::compose_scratch (pure host logic of the batch-scope flush)
+#include "batch_plan.hpp"  // ecg::schedule_groups, ecg::compose_scratch, ecg::BlockUse (the engine's pure host logic)
 #include "gf256.hpp"
 #include "matrix.hpp"  // ecg::compose_chain
 
@@ -492,6 +492,64 @@ static void chains() {
     printf("chains: %lld composed and checked, %lld left as chains\n", composed, refused);
 }
 
+// Block classification of the host tier (ecg::BlockUse, shared by the synchronous call, the deferred recording
+// and, for its validation half, the device tier) against a plain interpreter: random lists of 1-4 ops over up
+// to 12 block ids, ids repeated and written in place.  The interpreter walks the ops in order and marks a block
+// uploaded exactly when its first touch is a read.  Then the refusals: an id below 0, an id >= nblocks, a null
+// block.
+static void block_classes() {
+    ecg::BlockUse use;
+    uint8_t byte = 0;
+    long long checked = 0;
+    for (int trial = 0; trial < 4000; trial++) {
+        const int nb = rnd(1, 12);
+        std::vector<uint8_t*> blocks(nb, &byte);
+        std::vector<ecg::LinearOp> ops(rnd(1, 4));
+        for (auto& op : ops) {
+            const int k = rnd(0, 5), m = rnd(1, 3);
+            for (int j = 0; j < k; j++) op.src_ids.push_back(rnd(0, nb - 1));
+            for (int p = 0; p < m; p++) op.dst_ids.push_back(k && rnd(0, 3) == 0 ? op.src_ids[0] : rnd(0, nb - 1));
+            op.coef.assign((size_t)k * m, 1);
+        }
+        // 0 = untouched, 1 = first touched by a read, 2 = first touched by a write
+        std::vector<int> first(nb, 0);
+        std::vector<char> wr(nb, 0);
+        for (const auto& op : ops) {  // an op reads all its inputs before it writes
+            for (int id : op.src_ids)
+                if (!first[id]) first[id] = 1;
+            for (int id : op.dst_ids) {
+                if (!first[id]) first[id] = 2;
+                wr[id] = 1;
+            }
+        }
+        if (use.classify(ops, blocks.data(), nb) != ECG_OK) abort();
+        if ((int)use.upload.size() != nb || (int)use.written.size() != nb || (int)use.used.size() != nb) abort();
+        for (int id = 0; id < nb; id++) {
+            if ((use.upload[id] != 0) != (first[id] == 1) || (use.written[id] != 0) != (wr[id] != 0) ||
+                (use.used[id] != 0) != (first[id] != 0)) {
+                fprintf(stderr, "block classes: block %d differs from the interpreter (trial %d)\n", id, trial);
+                abort();
+            }
+        }
+        // one bad id or null block, in a random place, is refused
+        std::vector<ecg::LinearOp> bad = ops;
+        ecg::LinearOp& op = bad[(size_t)rnd(0, (int)bad.size() - 1)];
+        std::vector<int>& ids = (!op.src_ids.empty() && rnd(0, 1)) ? op.src_ids : op.dst_ids;
+        const size_t at = (size_t)rnd(0, (int)ids.size() - 1);
+        const int how = rnd(0, 2);
+        if (how == 0) ids[at] = -rnd(1, 3);
+        else if (how == 1) ids[at] = nb + rnd(0, 2);
+        else blocks[(size_t)ids[at]] = nullptr;
+        if (use.classify(bad, blocks.data(), nb) != ECG_EINVAL) {
+            fprintf(stderr, "block classes: refusal %d not refused (trial %d)\n", how, trial);
+            abort();
+        }
+        if (ecg::walk_block_ids(bad, blocks.data(), nb, [](int) {}, [](int) {}) != ECG_EINVAL) abort();
+        checked++;
+    }
+    printf("block classes: %lld op lists checked against the interpreter\n", checked);
+}
+
 static void batch_scope() {
     if (ecg_device_count() > 0) return;
     ecg_coding_parameters cp{};
@@ -524,6 +582,7 @@ int main() {
     grouping();
     scratch_composition();
     chains();
+    block_classes();
     batch_scope();
     printf("host fuzz done\n");
     return 0;

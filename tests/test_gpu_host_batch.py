@@ -1,4 +1,4 @@
-"""Deferred host-tier calls in a batch scope (ecg_batch_defer_host; engine.cpp record_host / host_flush).
+"""Deferred host-tier calls in a batch scope (ecg_batch_defer_host; host_tier.cpp record_host / host_flush).
 
 Config 1's shape is the reference's per-stripe host calls (proxy.cpp:312-349): RS(6,4) on 1 KiB blocks,
 one jerasure_matrix_encode per stripe.  Inside `with ecg.batch(host=True)` each call stages its inputs
@@ -158,6 +158,48 @@ def test_deferred_host_mixed_with_device_calls_and_large_blocks(ecg, oracle, tor
 
 def test_defer_host_outside_scope_refused(ecg, torch_cuda):
     assert ecg.lib().ecg_batch_defer_host(1) != 0
+
+
+@pytest.mark.parametrize("B", [4096, 4100])
+def test_deferred_host_mixed_plans_share_one_pointer_table(ecg, oracle, torch_cuda, B):
+    """Both ends of the mixed-plan pointer-table launch (engine.cpp run_ptr_batch_multi), RS(4,2), six deferred
+    one-block decodes.  First three distinct erasure patterns in shuffled order: calls of one shape with three
+    matrices, one launch with a program per matrix.  Then one pattern whose calls are kept apart by an encode
+    each, so every call holds its own copy of the one plan: the one-matrix shortcut (and the same for the
+    encodes).  B = 4100 adds a tail past the last 16 bytes.  Every block against the oracle."""
+    k, m, S = 4, 2, 6
+    rng = np.random.default_rng(B)
+    M = ecg.reed_sol_vandermonde_coding_matrix(k, m)
+    data, coding = _rs_stripes(rng, S, k, m, B)
+    for s in range(S):
+        oracle.jerasure_matrix_encode(k, m, M, data[s], coding[s], B)
+    originals = [[x.copy() for x in data[s] + coding[s]] for s in range(S)]
+
+    def erase(s, e):
+        (data[s] + coding[s])[e][:] = 0xEE
+
+    t0 = ecg.traffic_counters()["launches"]
+    with ecg.batch(host=True):
+        for s, e in enumerate([0, 2, 5, 2, 0, 5]):
+            erase(s, e)
+            assert ecg.jerasure_matrix_decode(k, m, M, 1, [e, -1], data[s], coding[s], B) == 0
+    t1 = ecg.traffic_counters()["launches"]
+    for s in range(S):
+        assert all(np.array_equal(a, b) for a, b in zip(data[s] + coding[s], originals[s])), ("shuffled", s)
+    again = [[np.zeros(B, np.uint8) for _ in range(m)] for _ in range(S)]
+    with ecg.batch(host=True):
+        for s in range(S):
+            erase(s, 1)
+            assert ecg.jerasure_matrix_decode(k, m, M, 1, [1, -1], data[s], coding[s], B) == 0
+            assert ecg.jerasure_matrix_encode(k, m, M, originals[s][:k], again[s], B) == 0
+    t2 = ecg.traffic_counters()["launches"]
+    # calls of one shape leave as ONE pointer-table launch whatever their matrices (plus the byte kernel for the
+    # tail when B is no multiple of 16): one shape in the first scope, two (decode, encode) in the second
+    per_group = 1 if B % 16 == 0 else 2
+    assert (t1 - t0, t2 - t1) == (per_group, 2 * per_group)
+    for s in range(S):
+        assert all(np.array_equal(a, b) for a, b in zip(data[s] + coding[s], originals[s])), ("apart", s)
+        assert all(np.array_equal(a, b) for a, b in zip(again[s], originals[s][k:])), ("encode", s)
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4])

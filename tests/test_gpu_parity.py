@@ -1021,7 +1021,7 @@ def test_row_split_of_separable_programs(ecg, oracle, torch_cuda, split):
 def test_host_pipeline_encode_decode(ecg, oracle, torch_cuda, pinned, B, S):
     """Host-resident batches, pinned and pageable, through the H2D -> kernel -> D2H pipeline (chunks not
     dividing S; 64 KiB and 1 MiB blocks, with and without padded device slots).  On pageable buffers a
-    second host thread issues the output copies (engine.cpp run_host_pipeline)."""
+    second host thread issues the output copies (host_pipeline.cpp run_host_pipeline)."""
     torch = torch_cuda
     k, m = 10, 4
     n = k + m
@@ -1090,7 +1090,7 @@ def test_host_tier_staging_paths(ecg, oracle, torch_cuda, zc):
 
 
 def test_zero_copy_completion_flags_back_to_back(ecg, oracle, torch_cuda):
-    """Zero-copy host calls complete by polled flags, never by a stream synchronize (engine.cpp
+    """Zero-copy host calls complete by polled flags, never by a stream synchronize (host_tier.cpp
     wait_flags): 1500 back-to-back calls on fresh data, each result read right after its flags, cycling
     through flagged shapes (1 KiB, 64 KiB: 32 workgroups, a 2-op decode) and ones that synchronize
     instead (B % 16 != 0: the byte kernel posts no flags), so a stale flag or an early read would show as

@@ -8,7 +8,7 @@ Eight threads issue 400 random operations each, at once.  Each operation is one 
 
 The coefficient-program cache is shrunk to 8 entries, so programs are evicted while other threads'
 launches may still use them.  Every result is compared with the oracle.  This test caught a GPU fault in
-an earlier design that registered the caller's pages for large host calls (see engine.cpp run_host).
+an earlier design that registered the caller's pages for large host calls (see host_tier.cpp run_host).
 """
 import os
 import random

@@ -57,7 +57,7 @@ def test_engine_concurrency_under_thread_sanitizer():
 @pytest.mark.skipif(not shutil.which("/opt/rocm/lib/llvm/bin/clang++"), reason="needs ROCm clang (TSan runtime)")
 def test_thread_sanitizer_reports_a_seeded_race():
     """The harness can see a race: the ECG_TEST_TSAN_SEEDED_RACE build pushes evicted program sets onto the
-    retirement list without its lock (engine.cpp Engine::retire), and ThreadSanitizer must say so."""
+    retirement list without its lock (program_cache.cpp Engine::retire), and ThreadSanitizer must say so."""
     rc, out, err = _tsan("seeded", 8, 100)
     assert rc != 0
     assert "WARNING: ThreadSanitizer: data race" in err, (out + err)[-3000:]

@@ -15,8 +15,8 @@ PG=""
 FLAGS="-O2 -g -fPIC $PG -Wno-unused-result"
 INC="-D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -I$PKG/csrc"
 pids=()
-for f in matrix engine codes planning capi; do
-  $CXX $FLAGS -std=c++17 $INC -x c++ -c $PKG/csrc/$f.cpp -o $OBJ/$f.o & pids+=($!)
+for f in $(make -s -C $PKG host-srcs); do  # the Makefile's HOST_SRCS
+  $CXX $FLAGS -std=c++17 $INC -x c++ -c $PKG/$f -o $OBJ/$(basename $f .cpp).o & pids+=($!)
 done
 ( $HIPCC $FLAGS -std=c++17 --offload-arch=gfx950 --offload-host-only -c $PKG/csrc/gf_kernels.hip -o $OBJ/gf_kernels.o \
     2>"$OBJ/gf_kernels.log" || { cat "$OBJ/gf_kernels.log" >&2; exit 1; } ) & pids+=($!)

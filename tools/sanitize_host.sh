@@ -14,8 +14,8 @@ HIPCC=/opt/rocm/bin/hipcc
 CXX="-O1 -g -std=c++17 -fPIC -Wall -Wno-unused-parameter -fno-omit-frame-pointer -fno-sanitize-recover=undefined"
 # the translation units compile in parallel; every status is checked
 pids=()
-for f in matrix engine codes planning capi; do
-  $HIPCC $CXX -fsanitize=address -fsanitize=undefined -fno-gpu-sanitize -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c $PKG/csrc/$f.cpp -o $OBJ/$f.o &
+for f in $(make -s -C $PKG host-srcs); do  # the Makefile's HOST_SRCS
+  $HIPCC $CXX -fsanitize=address -fsanitize=undefined -fno-gpu-sanitize -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c $PKG/$f -o $OBJ/$(basename $f .cpp).o &
   pids+=($!)
 done
 ( $HIPCC $CXX --offload-arch=gfx950 --offload-host-only -fsanitize=address -fsanitize=undefined -fno-gpu-sanitize \

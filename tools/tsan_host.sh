@@ -4,9 +4,9 @@
 # stand-in for the HIP runtime that emulates the library's kernels bit-exactly -- and the driver
 # tests/tsan/engine_race.cpp (8 threads of random proxy-like calls, every result against the oracle).
 #   tools/tsan_host.sh [variant] [threads] [ops] [seed]
-# variant "seeded" builds engine.cpp with -DECG_TEST_TSAN_SEEDED_RACE (retire() without its lock): the
-# run must then report a data race.  Variant "sharedkey" builds it with -DECG_TEST_PER_THREAD_SHARED_KEY
-# (round 4's retirement keying of hipStreamPerThread): the run must then report a device-time hazard in its
+# variant "seeded" builds them with -DECG_TEST_TSAN_SEEDED_RACE (program_cache.cpp: retire() without its lock):
+# the run must then report a data race.  Variant "sharedkey" builds them with -DECG_TEST_PER_THREAD_SHARED_KEY
+# (program_cache.cpp stream_key: round 4's retirement keying of hipStreamPerThread): the run must then report a device-time hazard in its
 # per-thread scenario (the stub's check that no table a pending launch reads is rewritten from another
 # stream).  tests/test_sanitize.py checks all three.
 set -euo pipefail
@@ -24,8 +24,8 @@ EXTRA=""
 [ "$VARIANT" = seeded ] && EXTRA="-DECG_TEST_TSAN_SEEDED_RACE"
 [ "$VARIANT" = sharedkey ] && EXTRA="-DECG_TEST_PER_THREAD_SHARED_KEY"
 pids=()
-for f in matrix engine codes planning capi; do
-  $CXX $FLAGS -std=c++17 $INC $EXTRA -x c++ -c $PKG/csrc/$f.cpp -o $OBJ/$f.o &
+for f in $(make -s -C $PKG host-srcs); do  # the Makefile's HOST_SRCS; $EXTRA reaches every one of them
+  $CXX $FLAGS -std=c++17 $INC $EXTRA -x c++ -c $PKG/$f -o $OBJ/$(basename $f .cpp).o &
   pids+=($!)
 done
 # its warnings (device-only attributes seen host-side) go to a log, printed if the compile fails
