@@ -95,6 +95,8 @@ int ecg_launch_histogram(long long* counts, int cap) {
     return launch_histogram(counts, cap);
 }
 
+int ecg_last_launch(int* v, int cap) { return last_launch(v, cap); }
+
 int ecg_set_option(int option, long long value) { return set_option(option, value) == 0 ? ECG_OK : ECG_EINVAL; }
 long long ecg_get_option(int option) { return get_option(option); }
 

@@ -844,6 +844,24 @@ int launch_histogram(long long* counts, int cap) {
     return ECG_HIST_SLOTS;
 }
 
+// Last-launch record (ecg_last_launch; gf_kernels.hpp last_launch names the fields): nine relaxed stores per
+// launch_gf call, as the check libraries' CheckLaunchLog keeps its six.  Diagnostics only: a reader racing a launch
+// may see fields of two launches.
+std::atomic<int> g_last[kGfLaunchFields] = {};
+
+static void record_launch(const GfLaunch& a, int grid_map, int map_group, int cols_per_wg, int wg_per_stripe, int mode,
+                          int kernel) {
+    const int v[kGfLaunchFields] = {grid_map, map_group,   cols_per_wg, wg_per_stripe, a.S,
+                                    a.rtiles, a.row_split, mode,        kernel};
+    for (int i = 0; i < kGfLaunchFields; ++i) g_last[i].store(v[i], std::memory_order_relaxed);
+}
+
+int last_launch(int* v, int cap) {
+    if (v && cap >= kGfLaunchFields)
+        for (int i = 0; i < kGfLaunchFields; ++i) v[i] = g_last[i].load(std::memory_order_relaxed);
+    return kGfLaunchFields;
+}
+
 hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st, int* n_wg) {
     if (n_wg) *n_wg = 0;
     if (base.k < 1 || base.m < 1 || base.S < 1 || base.B < 0 || base.MT < 1 ||
@@ -865,6 +883,7 @@ hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st
         Launcher l = a.binary ? pick_lat_dword_bin<true>(a.MT, a.k) : pick_lat_dword_bin<false>(a.MT, a.k);
         if (!l) return hipErrorInvalidValue;
         hist_lat(a.binary, a.MT, a.k, a.B);
+        record_launch(a, 0, 1, kLatThreads, (int)gx, mode, 2);  // gx workgroups of kLatThreads four-byte columns, linear
         const hipError_t e = l(a, dim3((unsigned)gx), st);
         if (e != hipSuccess) return e;
         if (n_wg) *n_wg = (int)gx;
@@ -899,6 +918,7 @@ hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st
         if (!l) return hipErrorInvalidValue;
         if (a.done_flags && (mode != GF_MODE_INLINE_LAT || vec_bytes < a.B)) return hipErrorInvalidValue;
         hist_vec(mode, a.binary, nt, a.MT);
+        record_launch(a, a.grid_map, a.map_group, a.cols_per_wg, a.wg_per_stripe, mode, 0);
         const hipError_t e = l(a, dim3((unsigned)gx, (unsigned)a.rtiles), st);
         if (e != hipSuccess) return e;
         if (n_wg) *n_wg = (int)(gx * a.rtiles);
@@ -924,6 +944,8 @@ hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st
         }
         if (!l) return hipErrorInvalidValue;
         hist_byte(mode == GF_MODE_INLINE_LAT ? (int)GF_MODE_INLINE : mode, a.binary, a.MT);
+        if (vec_bytes == 0)  // the byte kernel alone: cols_per_wg counts bytes, the map is linear
+            record_launch(a, 0, 1, a.cols_per_wg, a.wg_per_stripe, mode, 1);
         const hipError_t e = l(a, dim3((unsigned)gx, (unsigned)a.rtiles), st);
         if (e != hipSuccess) return e;
     }

@@ -71,7 +71,7 @@ EXPORTS = [
     "ecg_jerasure_invert_matrix", "ecg_jerasure_matrix_multiply", "ecg_galois_region_xor",
     "ecg_jerasure_matrix_encode", "ecg_jerasure_matrix_decode", "ecg_jerasure_matrix_dotprod",
     "ecg_batch_begin", "ecg_batch_flush", "ecg_batch_end", "ecg_batch_defer_host", "ecg_batch_scratch",
-    "ecg_batch_last_stats", "ecg_traffic_counters", "ecg_launch_histogram",
+    "ecg_batch_last_stats", "ecg_traffic_counters", "ecg_launch_histogram", "ecg_last_launch",
     "ecg_dev_matrix_encode", "ecg_dev_matrix_decode", "ecg_matrix_apply_batch", "ecg_matrix_apply_batch_multi",
     "ecg_encode_batch",
     "ecg_decode_batch", "ecg_perform_addition_batch", "ecg_make_decode_matrix", "ecg_region_xor_batch", "ecg_encode_batch_host", "ecg_decode_batch_host",
@@ -168,6 +168,7 @@ def lib():
         "ecg_batch_last_stats": ([ctypes.POINTER(LL)] * 4, I),
         "ecg_traffic_counters": ([ctypes.POINTER(LL)] * 2, I),
         "ecg_launch_histogram": ([ctypes.POINTER(LL), I], I),
+        "ecg_last_launch": ([IP, I], I),
         "ecg_device_count": ([], I),
         "ecg_set_device": ([I], I),
         "ecg_free": ([P], None),
@@ -443,6 +444,23 @@ def launch_histogram():
     v = (ctypes.c_longlong * n)()
     _check(lib().ecg_launch_histogram(v, n), "launch_histogram")
     return {hist_key(i): c for i, c in enumerate(v) if c}
+
+
+LAST_LAUNCH_FIELDS = ("grid_map", "map_group", "cols_per_wg", "wg_per_stripe", "S", "rtiles", "row_split", "mode",
+                      "kernel")
+
+
+def last_launch():
+    """Geometry of the process's most recent region-product call that launched a kernel, as placed in the launch
+    descriptor after the fallbacks (include/ecg.h ecg_last_launch): {grid_map, map_group, cols_per_wg, wg_per_stripe,
+    S, rtiles, row_split, mode, kernel}, all zero before the first.  kernel: 0 the 16-byte-column kernel (which the
+    geometry describes), 1 the byte kernel only, 2 the latency kernel."""
+    n = lib().ecg_last_launch(None, 0)
+    if n != len(LAST_LAUNCH_FIELDS):
+        raise EcgError(ECG_EINVAL, f"last_launch: library has {n} fields, binding {len(LAST_LAUNCH_FIELDS)}")
+    v = (ctypes.c_int * n)()
+    lib().ecg_last_launch(v, n)
+    return dict(zip(LAST_LAUNCH_FIELDS, (int(x) for x in v)))
 
 
 def dev_matrix_encode(k, m, matrix, data, coding, B, stream=None):

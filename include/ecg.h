@@ -254,6 +254,24 @@ int ecg_traffic_counters(long long* launches, long long* bytes);
 #define ECG_HIST_LAT 608
 #define ECG_HIST_SLOTS 800
 int ecg_launch_histogram(long long* counts, int cap);
+/* Geometry of this process's most recent region-product call that launched a kernel (diagnostics, read-only: how the
+ * launch rule placed it after ECG_OPT_GRID_MAP, ECG_OPT_MAP_GROUP, ECG_OPT_COLS_PER_WG, ECG_OPT_ROW_SPLIT and their
+ * fallbacks; all zero before the first).  Nine values, in order, the first six those of ecg_scrub_last_launch:
+ *   grid_map        workgroup -> chunk map: 0 linear, 1 XCD-contiguous, 2 stripe runs per XCD group.  The auto rule
+ *                   (ECG_OPT_GRID_MAP 3) resolves to 1 when the outputs are blocks of the input stripes, else to 2; a
+ *                   pointer-table launch takes 2 only when every call's outputs lie apart from its inputs
+ *   map_group       launch stripes per run of map 2, after halving until S is a multiple of 8 * map_group
+ *   cols_per_wg     16-byte columns of every block per workgroup
+ *   wg_per_stripe   workgroups per launch stripe; grid.x = S * wg_per_stripe
+ *   S               launch stripes: stripes times row_split when the rows were split
+ *   rtiles          row tiles (grid.y)
+ *   row_split       rows per program run as launch stripes of their own (ECG_OPT_ROW_SPLIT), 0 when not split
+ *   mode            the launch's addressing mode, numbered as in ecg_launch_histogram
+ *   kernel          0: the call ran the 16-byte-column kernel (and the byte kernel on what that left over), which the
+ *                   geometry describes; 1: the byte kernel only (cols_per_wg then counts bytes); 2: the latency
+ *                   kernel (cols_per_wg then counts its 4-byte columns, S = 1)
+ * Returns 9; v is written when cap >= 9 (v may be NULL otherwise). */
+int ecg_last_launch(int* v, int cap);
 /* Generic region product: out[dst_ids[p]] = XOR_j coef[p*k_in+j] * in[src_ids[j]] for S stripes,
  * in block b of stripe s at in_base + s*in_sstride + b*in_bstride (likewise out). */
 int ecg_matrix_apply_batch(int k_in, int m_out, const int* coef, const int* src_ids, const int* dst_ids,

@@ -101,8 +101,9 @@ def live_rows(c, M):
     return [p for p in range(c.m) if M[p].any()]
 
 
-def expected_keys(c, M=None):
-    """{key: launches} of the case, by the dispatcher's rules."""
+def _route(c, M):
+    """(binary, mt, rtiles, vec_bytes, mode, lat) of the case's launch_gf call, by the dispatcher's rules; lat: the
+    call runs the latency kernel."""
     M = matrix(c) if M is None else M
     rows = live_rows(c, M)
     binary = int(all(int(v) <= 1 for p in rows for v in M[p]))  # matrix.cpp op_is_binary
@@ -117,9 +118,16 @@ def expected_keys(c, M=None):
         mode = MODE_INLINE_LAT  # host_tier.cpp run_host: launch_one(..., latency = true)
     else:  # engine.cpp launch_one: lat = B <= ECG_OPT_LAT_DWORD_BYTES && k <= kLatMaxSrc
         mode = MODE_INLINE_LAT if c.B <= c.lat and c.k <= LAT_MAX_SRC else MODE_INLINE
+    lat = (mode == MODE_INLINE_LAT and vec_bytes == c.B and c.B <= c.lat and c.k <= LAT_MAX_SRC and rtiles == 1 and
+           mt <= K_MAX_MT)  # gf_kernels.hip launch_gf
+    return binary, mt, rtiles, vec_bytes, mode, lat
+
+
+def expected_keys(c, M=None):
+    """{key: launches} of the case, by the dispatcher's rules."""
+    binary, mt, rtiles, vec_bytes, mode, lat = _route(c, M)
     keys = {}
-    if (mode == MODE_INLINE_LAT and vec_bytes == c.B and c.B <= c.lat and c.k <= LAT_MAX_SRC and rtiles == 1 and
-            mt <= K_MAX_MT):  # gf_kernels.hip launch_gf
+    if lat:
         keys[("lat", binary, mt, lat_bucket(c.k), int(c.B <= LAT_EAGER_BYTES))] = 1
         return keys
     if vec_bytes > 0:
@@ -127,6 +135,14 @@ def expected_keys(c, M=None):
     if vec_bytes < c.B:
         keys[("byte", MODE_INLINE if mode == MODE_INLINE_LAT else mode, binary, mt)] = 1
     return keys
+
+
+def expected_report(c, M=None):
+    """{mode, rtiles, kernel} of ecg.last_launch() after the case's call (include/ecg.h ecg_last_launch): the mode
+    the call was launched in (an INLINE_LAT call's byte kernel still reports mode 3), its row tiles, and kernel 2 for
+    the latency kernel, 0 when a vector launch ran, 1 for the byte kernel alone."""
+    _, _, rtiles, vec_bytes, mode, lat = _route(c, M)
+    return {"mode": mode, "rtiles": rtiles, "kernel": 2 if lat else 0 if vec_bytes > 0 else 1}
 
 
 B_MAIN = 4693   # two full 2 KiB workgroup chunks, a partial third of 37 columns, a 5-byte tail

@@ -5,18 +5,20 @@ tests/gf_kernel_cases.py lists the cases: one public call each, with the instant
 on.  A case snapshots ecg.launch_histogram() and the launch counter, makes its call, and asserts that the
 histogram moved on exactly the declared keys and that those account for every launch counted; then it compares
 the whole output arena -- the named blocks, the 64-byte bands of 0xC3 around every block, the blocks the op does
-not name (0x3C) -- with the expected image, and the input arena with what was uploaded.  So a store past a
-block's end, a dead lane or a dead row of a short last tile that stores, and a call routed to another kernel
-than the one declared all fail here.  The last test (no GPU) checks that the declared keys cover the enumeration
+not name (0x3C) -- with the expected image, and the input arena with what was uploaded (tests/gf_arena.py).  So a
+store past a block's end, a dead lane or a dead row of a short last tile that stores, and a call routed to another
+kernel than the one declared all fail here.  ecg.last_launch() must report the mode, the row tiles and the kernel
+class the case declares.  The last test (no GPU) checks that the declared keys cover the enumeration
 tests/test_kernel_enumeration.py pins against the code object.
 """
 import numpy as np
 import pytest
 
+import gf_arena as A
 import gf_kernel_cases as C
 import gf_plain
 
-GUARD, BAND, FILL = 64, 0xC3, 0x3C
+GUARD = A.GUARD
 gpu = pytest.mark.gpu
 
 
@@ -28,38 +30,17 @@ def torch_cuda():
     return torch
 
 
-def _pitch(B):
-    return (GUARD + B + GUARD + 15) & ~15  # every block 16-byte aligned in an aligned arena
-
-
-def _to_dev(torch, img, shift):
-    flat = torch.empty(img.size + 16, dtype=torch.uint8, device="cuda")
-    view = flat[shift:shift + img.size]
-    view.copy_(torch.from_numpy(img.reshape(-1)))
-    return view.view(img.shape)
-
-
-def _where(idx, shape, B, dst):
-    s, slot, off = np.unravel_index(idx, shape)
-    if off < GUARD or off >= GUARD + B:
-        return f"guard band of stripe {s} slot {slot} at byte {off - GUARD} of the block"
-    if slot not in dst:
-        return f"untouched block: stripe {s} slot {slot} byte {off - GUARD}"
-    return None
-
-
 def run_case(ecg, torch, c, M=None, fill_in=None, describe=None):
     """One case: set its options, make its call, check the histogram, the outputs, the bands and the inputs."""
     M = C.matrix(c) if M is None else np.asarray(M, dtype=np.int64)
-    rows, keys = C.live_rows(c, M), C.expected_keys(c, M)
+    rows, keys, report = C.live_rows(c, M), C.expected_keys(c, M), C.expected_report(c, M)
     k, m, B = c.k, c.m, c.B
     pos = {"strided": (0, 1, 2), "ptrs": (0, 1, 3)}.get(c.form, (0,))  # ptrs: no single stripe stride
-    NS, P, n_in, n_out = pos[-1] + 1, _pitch(B), k + 1, m + 2
+    NS, n_in, n_out = pos[-1] + 1, k + 1, m + 2
     rng = np.random.default_rng(c.seed ^ 0x5EED)
-    in_img = np.full((NS, n_in, P), BAND, np.uint8)
+    in_img = A.blank(NS, n_in, B)
     in_img[:, :, GUARD:GUARD + B] = rng.integers(0, 256, (NS, n_in, B), dtype=np.uint8) if fill_in is None else fill_in
-    out_img = np.full((NS, n_out, P), BAND, np.uint8)
-    out_img[:, :, GUARD:GUARD + B] = FILL
+    out_img = A.blank(NS, n_out, B)
     src, dst = [k - j for j in range(k)], [p + 1 for p in range(m)]  # slot 0 (and m + 1 of the outputs) unnamed
     want = out_img.copy()
     for s in pos:
@@ -79,7 +60,7 @@ def run_case(ecg, torch, c, M=None, fill_in=None, describe=None):
                                        [got[0, dst[p], GUARD:GUARD + B] for p in range(m)], B)
             in_after = h_in
         else:
-            d_in, d_out = _to_dev(torch, in_img, c.shift), _to_dev(torch, out_img, c.shift)
+            d_in, d_out = A.to_dev(torch, in_img, c.shift), A.to_dev(torch, out_img, c.shift)
             torch.cuda.synchronize()
             h0, l0 = ecg.launch_histogram(), ecg.traffic_counters()["launches"]
             if c.form == "strided":
@@ -96,7 +77,7 @@ def run_case(ecg, torch, c, M=None, fill_in=None, describe=None):
                     call(0)
             torch.cuda.synchronize()
             got, in_after = d_out.cpu().numpy(), d_in.cpu().numpy()
-        h1, l1 = ecg.launch_histogram(), ecg.traffic_counters()["launches"]
+        h1, l1, last = ecg.launch_histogram(), ecg.traffic_counters()["launches"], ecg.last_launch()
     finally:
         for o, v in enumerate(saved):
             ecg.set_option(o, v)
@@ -104,16 +85,13 @@ def run_case(ecg, torch, c, M=None, fill_in=None, describe=None):
     delta = {key: n for key, n in delta.items() if n}
     assert delta == keys, (c, "launched", delta, "declared", keys)
     assert l1 - l0 == sum(keys.values()), (c, l1 - l0, keys)
+    assert {f: last[f] for f in report} == report, (c, "reported", last, "declared", report)
     assert np.array_equal(in_after, in_img), (c, "an input arena changed")
-    if not np.array_equal(got, want):
-        bad = np.flatnonzero(got.reshape(-1) != want.reshape(-1))
-        outside = [w for w in (_where(i, got.shape, B, dst) for i in bad[:4096]) if w]
-        assert not outside, (c, f"{len(bad)} bytes differ; written outside the named blocks", outside[:4])
-        s, slot, off = (int(v) for v in np.unravel_index(bad[0], got.shape))
-        p, o = dst.index(slot), off - GUARD
-        msg = describe(M, p, o, in_img[s, src, GUARD:GUARD + B]) if describe else ""
-        raise AssertionError(f"{c}: {len(bad)} bytes differ; first at stripe {s} output row {p} byte {o}: "
-                             f"got {got[s, slot, off]:#04x}, want {want[s, slot, off]:#04x} {msg}")
+
+    def name(s, slot, o):
+        msg = describe(M, dst.index(slot), o, in_img[s, src, GUARD:GUARD + B]) if describe else ""
+        return f"(output row {dst.index(slot)}) {msg}"
+    A.assert_same(got, want, B, lambda s, slot: slot in dst, c, name)
     return keys
 
 

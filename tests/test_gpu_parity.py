@@ -958,7 +958,9 @@ def test_row_split_of_separable_programs(ecg, oracle, torch_cuda, split):
     size run one launch stripe per (stripe, row).  Same bytes as the unsplit launch, for a BINARY 40 -> 5 PC
     merge shape, a GENERAL 16 -> 2 with two programs per launch over a stripe subset, tails and unaligned
     block sizes; and an in-place op whose outputs are inputs of other rows is never split (its rows must all
-    read before any writes)."""
+    read before any writes).  ecg.last_launch() shows what ran: 5, 2 and 0 rows per program as launch stripes of
+    their own at 16, no split anywhere at 0.  (The stripe-subset op splits only into a buffer with the input's stripe
+    stride; into the [S][2][B] buffer this test used alone until the report existed, it never did.)"""
     torch = torch_cuda
     saved = ecg.get_option(ecg.ECG_OPT_ROW_SPLIT)
     rng = random.Random(5)
@@ -973,6 +975,8 @@ def test_row_split_of_separable_programs(ecg, oracle, torch_cuda, split):
         progs = [(coef, src, [4, 0, 3, 1, 2])]
         out = torch.zeros((S, 5, B), dtype=torch.uint8, device="cuda")
         ecg.matrix_apply_batch_multi(progs, d_in, out)
+        last = ecg.last_launch()
+        assert (last["row_split"], last["S"]) == ((5, 5 * S) if split else (0, S)), last
         torch.cuda.synchronize()
         assert np.array_equal(out.cpu().numpy(), _apply_ref(oracle, progs, [0] * S, d_in.cpu().numpy(), S, B, 5))
         # GENERAL 16 -> 2, two programs (different row supports), stripe subset, B not a multiple of 16
@@ -986,18 +990,29 @@ def test_row_split_of_separable_programs(ecg, oracle, torch_cuda, split):
             progs.append((cf, src, [1, 0]))
         subset = sorted(rng.sample(range(S), 13))
         which = [rng.randrange(2) for _ in subset]
-        out = torch.zeros((S, 2, B), dtype=torch.uint8, device="cuda")
-        ecg.matrix_apply_batch_multi(progs, d_in, out, prog_of_stripe=torch.tensor(which, dtype=torch.int32,
-                                                                                    device="cuda"),
-                                     stripe_of=torch.tensor(subset, dtype=torch.int32, device="cuda"))
-        torch.cuda.synchronize()
-        hin, hout = d_in.cpu().numpy(), out.cpu().numpy()
         wfull = [0] * S
         for s, w in zip(subset, which):
             wfull[s] = w
+        hin = d_in.cpu().numpy()
         ref = _apply_ref(oracle, progs, wfull, hin, S, B, 2)
-        for s in range(S):
-            assert np.array_equal(hout[s], ref[s]) if s in subset else not hout[s].any(), s
+        # With a stripe subset the host cannot bound the stripes the launch addresses, so it splits only where input
+        # and output share a stripe stride and no output block comes within B bytes of an input block of its stripe
+        # (engine.cpp row_split): into a view of a buffer shaped like the input it splits, into a buffer with a stripe
+        # stride of its own it does not, at either setting.
+        for same_stride in (True, False):
+            backing = torch.zeros((S, n if same_stride else 2, B), dtype=torch.uint8, device="cuda")
+            out = backing[:, :2]
+            ecg.matrix_apply_batch_multi(progs, d_in, out, prog_of_stripe=torch.tensor(which, dtype=torch.int32,
+                                                                                        device="cuda"),
+                                         stripe_of=torch.tensor(subset, dtype=torch.int32, device="cuda"))
+            last = ecg.last_launch()
+            want = (2, 2 * len(subset)) if split and same_stride else (0, len(subset))
+            assert (last["row_split"], last["S"]) == want, (same_stride, last)
+            torch.cuda.synchronize()
+            hout = backing.cpu().numpy()
+            assert not hout[:, 2:].any()
+            for s in range(S):
+                assert np.array_equal(hout[s, :2], ref[s]) if s in subset else not hout[s].any(), (same_stride, s)
         # in place: row 0 writes block 16 (an input of row 1), row 1 writes block 0 (an input of row 0)
         S, B = 6, 65536
         d = torch.empty((S, 32, B), dtype=torch.uint8, device="cuda")
@@ -1006,6 +1021,8 @@ def test_row_split_of_separable_programs(ecg, oracle, torch_cuda, split):
         cf = [[1 if (j < 16) == (r == 0) else 0 for j in range(32)] for r in range(2)]
         progs = [(cf, list(range(32)), [16, 0])]
         ecg.matrix_apply_batch_multi(progs, d, d)
+        last = ecg.last_launch()
+        assert (last["row_split"], last["S"]) == (0, S), last       # in place: refused at either setting
         torch.cuda.synchronize()
         ref = h0.copy()
         for s in range(S):
@@ -1118,7 +1135,10 @@ def test_zero_copy_completion_flags_back_to_back(ecg, oracle, torch_cuda):
 def test_tuning_options_never_change_results(ecg, oracle, torch_cuda):
     """Every ECG_OPT_* setting (grid map incl. auto, map-2 stripe groups, NT policy, chunk size) gives
     identical bytes, for an in-stripe encode, a separate-buffer decode and S values that do / do not
-    divide by 8 (and by 8 G: G = 3 falls back to 1, G = 4 runs as is at S = 32)."""
+    divide by 8 (and by 8 G: G = 3 falls back to 1, G = 4 runs as is at S = 32).  ecg.last_launch() after each
+    call is what the launch rule's mirror (tests/gf_geometry_cases.py) gives for the setting: the encode's auto map
+    is 1, the decode's 2, and every fallback is the one the setting calls for."""
+    from gf_geometry_cases import expected_gf_geometry
     torch = torch_cuda
     k, m, B = 10, 4, 3 * 8192 + 16
     n = k + m
@@ -1138,8 +1158,13 @@ def test_tuning_options_never_change_results(ecg, oracle, torch_cuda):
                 ecg.set_option(ecg.ECG_OPT_COLS_PER_WG, cpw)
                 stripes[:, k:].fill_(0xA5)
                 ecg.encode_batch(k, m, M, stripes[:, :k], stripes[:, k:])
+                rest = {"rtiles": 1, "row_split": 0, "mode": 2, "kernel": 0}
+                assert ecg.last_launch() == dict(expected_gf_geometry(S, B, gmap, grp, cpw, True), **rest), (
+                    "encode", S, gmap, grp, nt, cpw)
                 out = torch.full((S, 1, B), 0x3C, dtype=torch.uint8, device="cuda")
                 ecg.decode_batch(k, m, M, 1, [[e] for e in range(n)], stripes, out=out, pattern_of_stripe=pos)
+                assert ecg.last_launch() == dict(expected_gf_geometry(S, B, gmap, grp, cpw, False), **rest), (
+                    "decode", S, gmap, grp, nt, cpw)
                 torch.cuda.synchronize()
                 if ref_par is None:
                     ref_par, ref_dec = stripes[:, k:].clone(), out.clone()
