@@ -24,7 +24,8 @@
 #include <atomic>
 
 #include "gf_kernels.hpp"
-#include "gf256.hpp"
+// the host side's launch rule, launch log and row-count switch, shared with the check libraries
+#include "launch_rule.hpp"
 
 // gfx950 only: the completion-flag epilogue (gf_done_flag.hpp) encodes its waits for gfx9's vmcnt, which
 // counts stores there; gfx10+ count stores in vscnt, and the flag could then overtake the data.
@@ -381,6 +382,7 @@ __device__ __forceinline__ void worker_call(const unsigned* d, CoefTab* wt) {
     }
 }
 
+// the host's kLatBuckets, written out (taking the list here moved the kernel's code)
 template <int MT, bool BIN>
 __device__ __forceinline__ void worker_call_k(const unsigned* d, CoefTab* wt) {
     const unsigned k = d[worker_pos(WF_K)];
@@ -531,32 +533,7 @@ __global__ void __launch_bounds__(kThreads) fill_splitmix_kernel(uint8_t* dst, l
 }
 
 // ---------------------------------------------------------------------------------------------
-// Dispatch
-
-std::atomic<long long> g_opt[ECG_OPT_COUNT] = {};
-std::atomic<int> g_opt_init{0};
-
-void init_options() {
-    if (g_opt_init.load(std::memory_order_acquire)) return;
-    auto env = [](const char* n, long long d) {
-        const char* e = getenv(n);
-        return e ? atoll(e) : d;
-    };
-    g_opt[ECG_OPT_NT].store(env("ECG_NT", 3));
-    g_opt[ECG_OPT_COLS_PER_WG].store(env("ECG_COLS_PER_WG", 0));
-    g_opt[ECG_OPT_GRID_MAP].store(env("ECG_GRID_MAP", 3));
-    // every staged call (r02 host_latency.py --sweep-zc: zero-copy with completion flags beats DMA staging
-    // at every block size up to kStagedMaxBlock)
-    g_opt[ECG_OPT_ZEROCOPY_BYTES].store(env("ECG_ZEROCOPY_BYTES", 8 << 20));
-    g_opt[ECG_OPT_PROGRAM_CACHE].store(env("ECG_PROGRAM_CACHE", 4096));
-    g_opt[ECG_OPT_MAP_GROUP].store(env("ECG_MAP_GROUP", 1));
-    g_opt[ECG_OPT_LAT_DWORD_BYTES].store(env("ECG_LAT_DWORD_BYTES", 1 << 20));
-    g_opt[ECG_OPT_CALL_WORKER].store(env("ECG_CALL_WORKER", 0));
-    g_opt[ECG_OPT_ROW_SPLIT].store(env("ECG_ROW_SPLIT", 16));
-    g_opt[ECG_OPT_GRAVEYARD].store(env("ECG_GRAVEYARD", 16384));
-    g_opt[ECG_OPT_MT1_LDS_PAD].store(env("ECG_MT1_LDS_PAD", -1));
-    g_opt_init.store(1, std::memory_order_release);
-}
+// Dispatch (the options are read through get_option: gf_host.cpp)
 
 // Launchers return the status of THEIR launch (hipLaunchKernel's return value): the thread's sticky
 // last error (hipGetLastError) also holds errors of earlier runtime calls the caller made and handled, and
@@ -596,7 +573,7 @@ hipError_t launch_with(F kernel, const GfLaunch& a, dim3 grid, hipStream_t st) {
 // GENERAL launches of 3+ outputs (the encode) lose at every pad and take none; two-output launches: mt2_lds_pad;
 // BINARY tiles of 8-9 outputs: gen_launch.
 unsigned mt1_lds_pad(int k, bool ptrs) {
-    const long long opt = g_opt[ECG_OPT_MT1_LDS_PAD].load(std::memory_order_relaxed);
+    const long long opt = get_option(ECG_OPT_MT1_LDS_PAD);
     if (opt >= 0) return (unsigned)opt;
     if (k <= 1) return 0;
     if (k <= 3) return 12288;
@@ -615,7 +592,7 @@ unsigned mt1_lds_pad(int k, bool ptrs) {
 // ECG_OPT_MT1_LDS_PAD for them too (tuning only).
 unsigned mt2_lds_pad(int k) {
 #ifdef ECG_TUNE_PAD_MT2
-    const long long opt = g_opt[ECG_OPT_MT1_LDS_PAD].load(std::memory_order_relaxed);
+    const long long opt = get_option(ECG_OPT_MT1_LDS_PAD);
     if (opt >= 0) return (unsigned)opt;
 #endif
     return k <= 7 ? 0u : k <= 11 ? 20480u : 24576u;
@@ -625,7 +602,7 @@ template <int MT, int MODE, int NT, bool BIN>
 hipError_t gen_launch(const GfLaunch& a, dim3 g, hipStream_t st) {
 #ifdef ECG_TUNE_PAD_MT_LO  // tuning builds only: ECG_OPT_MT1_LDS_PAD caps launches of MT_LO..MT_HI outputs too
     if constexpr (MT >= ECG_TUNE_PAD_MT_LO && MT <= ECG_TUNE_PAD_MT_HI) {
-        const long long opt = g_opt[ECG_OPT_MT1_LDS_PAD].load(std::memory_order_relaxed);
+        const long long opt = get_option(ECG_OPT_MT1_LDS_PAD);
         return launch_kernel_lds(gf_vec_kernel<MT, MODE, NT, BIN>, g, dim3(kThreads), opt > 0 ? (unsigned)opt : 0u, st, a);
     }
 #endif
@@ -640,34 +617,19 @@ hipError_t gen_launch(const GfLaunch& a, dim3 g, hipStream_t st) {
     return launch_kernel_lds(gf_vec_kernel<MT, MODE, NT, BIN>, g, dim3(kThreads), lds, st, a);
 }
 
+// one(std::integral_constant<int, MT>()) for a tile of MT rows: 1 to 8, and, where WIDE, the wide BINARY tiles of 9 to
+// 16 rows (kMaxMTBin); else null
+template <bool WIDE, class F>
+Launcher pick_mt(int MT, F one) {
+    if (MT <= 8) return pick_of8<1, Launcher>(MT, nullptr, one);
+    if constexpr (WIDE) return pick_of8<9, Launcher>(MT, nullptr, one);
+    return nullptr;
+}
+
 template <int MODE, int NT, bool BIN>
 Launcher gen_pick(int MT) {
-    switch (MT) {
-        case 1: return gen_launch<1, MODE, NT, BIN>;
-        case 2: return gen_launch<2, MODE, NT, BIN>;
-        case 3: return gen_launch<3, MODE, NT, BIN>;
-        case 4: return gen_launch<4, MODE, NT, BIN>;
-        case 5: return gen_launch<5, MODE, NT, BIN>;
-        case 6: return gen_launch<6, MODE, NT, BIN>;
-        case 7: return gen_launch<7, MODE, NT, BIN>;
-        case 8: return gen_launch<8, MODE, NT, BIN>;
-        default: break;
-    }
-    // wide BINARY tiles (kMaxMTBin): only the default NT policy is built (launch_gf runs them with it)
-    if constexpr (BIN && NT == 3) {
-        switch (MT) {
-            case 9: return gen_launch<9, MODE, NT, BIN>;
-            case 10: return gen_launch<10, MODE, NT, BIN>;
-            case 11: return gen_launch<11, MODE, NT, BIN>;
-            case 12: return gen_launch<12, MODE, NT, BIN>;
-            case 13: return gen_launch<13, MODE, NT, BIN>;
-            case 14: return gen_launch<14, MODE, NT, BIN>;
-            case 15: return gen_launch<15, MODE, NT, BIN>;
-            case 16: return gen_launch<16, MODE, NT, BIN>;
-            default: break;
-        }
-    }
-    return nullptr;
+    // wide BINARY tiles: only the default NT policy is built (launch_gf runs them with it)
+    return pick_mt<BIN && NT == 3>(MT, [](auto mt) -> Launcher { return gen_launch<decltype(mt)::value, MODE, NT, BIN>; });
 }
 
 template <int MODE, int NT>
@@ -702,30 +664,28 @@ hipError_t lat_dword_launch(const GfLaunch& a, dim3 g, hipStream_t st) {
 
 // input-count buckets of the latency kernel: exact for the BASELINE shapes (RS(6,4), RS(10,4) encode and
 // decode, Azure-LRC(12,2,2) global rows), at most 3 padded inputs elsewhere
+constexpr int kLatBuckets[] = {4, 6, 8, 10, 12, 16};
+constexpr int kLatBucketCount = sizeof(kLatBuckets) / sizeof(kLatBuckets[0]);
+static_assert(kLatBuckets[kLatBucketCount - 1] == kLatMaxSrc && kLatBucketCount <= 8, "pick_lat_k switches over 8");
+
+// index of the least bucket that holds k inputs (kLatBucketCount: none does)
+constexpr int lat_bucket(int k) {
+    int b = 0;
+    while (b < kLatBucketCount && k > kLatBuckets[b]) ++b;
+    return b;
+}
+
 template <int MT, bool BIN>
 Launcher pick_lat_k(int k) {
-    if (k <= 4) return lat_dword_launch<MT, BIN, 4>;
-    if (k <= 6) return lat_dword_launch<MT, BIN, 6>;
-    if (k <= 8) return lat_dword_launch<MT, BIN, 8>;
-    if (k <= 10) return lat_dword_launch<MT, BIN, 10>;
-    if (k <= 12) return lat_dword_launch<MT, BIN, 12>;
-    if (k <= 16) return lat_dword_launch<MT, BIN, 16>;
-    return nullptr;
+    return pick_of8<0, Launcher>(lat_bucket(k), nullptr, [](auto b) -> Launcher {
+        if constexpr (decltype(b)::value < kLatBucketCount) return lat_dword_launch<MT, BIN, kLatBuckets[decltype(b)::value]>;
+        else return nullptr;
+    });
 }
 
 template <bool BIN>
 Launcher pick_lat_dword_bin(int MT, int k) {
-    switch (MT) {
-        case 1: return pick_lat_k<1, BIN>(k);
-        case 2: return pick_lat_k<2, BIN>(k);
-        case 3: return pick_lat_k<3, BIN>(k);
-        case 4: return pick_lat_k<4, BIN>(k);
-        case 5: return pick_lat_k<5, BIN>(k);
-        case 6: return pick_lat_k<6, BIN>(k);
-        case 7: return pick_lat_k<7, BIN>(k);
-        case 8: return pick_lat_k<8, BIN>(k);
-        default: return nullptr;
-    }
+    return pick_of8<1, Launcher>(MT, nullptr, [k](auto mt) { return pick_lat_k<decltype(mt)::value, BIN>(k); });
 }
 
 template <int MT, int MODE, bool BIN>
@@ -735,31 +695,7 @@ hipError_t byte_launch(const GfLaunch& a, dim3 g, hipStream_t st) {
 
 template <int MODE, bool BIN>
 Launcher pick_byte_bin(int MT) {
-    switch (MT) {
-        case 1: return byte_launch<1, MODE, BIN>;
-        case 2: return byte_launch<2, MODE, BIN>;
-        case 3: return byte_launch<3, MODE, BIN>;
-        case 4: return byte_launch<4, MODE, BIN>;
-        case 5: return byte_launch<5, MODE, BIN>;
-        case 6: return byte_launch<6, MODE, BIN>;
-        case 7: return byte_launch<7, MODE, BIN>;
-        case 8: return byte_launch<8, MODE, BIN>;
-        default: break;
-    }
-    if constexpr (BIN) {
-        switch (MT) {
-            case 9: return byte_launch<9, MODE, BIN>;
-            case 10: return byte_launch<10, MODE, BIN>;
-            case 11: return byte_launch<11, MODE, BIN>;
-            case 12: return byte_launch<12, MODE, BIN>;
-            case 13: return byte_launch<13, MODE, BIN>;
-            case 14: return byte_launch<14, MODE, BIN>;
-            case 15: return byte_launch<15, MODE, BIN>;
-            case 16: return byte_launch<16, MODE, BIN>;
-            default: break;
-        }
-    }
-    return nullptr;
+    return pick_mt<BIN>(MT, [](auto mt) -> Launcher { return byte_launch<decltype(mt)::value, MODE, BIN>; });
 }
 
 template <int MODE>
@@ -768,30 +704,6 @@ Launcher pick_byte(const GfLaunch& a) {
 }
 
 }  // namespace
-
-long long get_option(int opt) {
-    init_options();
-    if (opt < 0 || opt >= ECG_OPT_COUNT) return -1;
-    return g_opt[opt].load();
-}
-
-int set_option(int opt, long long value) {
-    init_options();
-    if (opt < 0 || opt >= ECG_OPT_COUNT) return -1;
-    if (opt == ECG_OPT_NT && (value < 0 || value > 3)) return -1;
-    if (opt == ECG_OPT_COLS_PER_WG && (value < 0 || (value % kThreads) != 0)) return -1;
-    if (opt == ECG_OPT_GRID_MAP && (value < 0 || value > 3)) return -1;
-    if (opt == ECG_OPT_ZEROCOPY_BYTES && value < 0) return -1;
-    if (opt == ECG_OPT_PROGRAM_CACHE && value < 2) return -1;
-    if (opt == ECG_OPT_MAP_GROUP && (value < 1 || value > (1 << 20))) return -1;
-    if (opt == ECG_OPT_LAT_DWORD_BYTES && value < 0) return -1;
-    if (opt == ECG_OPT_CALL_WORKER && (value < 0 || value > 1000000)) return -1;  // idle limit <= 1 s
-    if (opt == ECG_OPT_ROW_SPLIT && value < 0) return -1;
-    if (opt == ECG_OPT_GRAVEYARD && value < 1) return -1;
-    if (opt == ECG_OPT_MT1_LDS_PAD && (value < -1 || value > 65536)) return -1;
-    g_opt[opt].store(value);
-    return 0;
-}
 
 // Grid-map auto rule (profiles/r01/shape_sweep.py, every k_in x m_out shape): when the outputs are blocks
 // of the input stripes themselves (encode: [S][k+m][B]), XCD-contiguous chunks (map 1) are 1-3 % faster;
@@ -808,13 +720,13 @@ static bool outputs_in_stripe(const GfLaunch& a, int mode) {
 
 // Process-wide traffic counters (ecg_traffic_counters): region-product kernels launched, and the bytes they move
 // as planned -- every row tile reads the launch's k inputs, every output is written once: S * B * (rtiles * k + m)
-// per region product.  Relaxed atomics: two uncontended adds per launch.
-std::atomic<long long> g_launched{0}, g_moved{0};
+// per region product.  With them the last-launch record (ecg_last_launch; gf_kernels.hpp last_launch names the nine
+// fields): two uncontended relaxed adds and nine relaxed stores per launch_gf call.
+static LaunchLog<kGfLaunchFields> g_gf_log;
 
-void launch_traffic(long long* launches, long long* bytes) {
-    if (launches) *launches = g_launched.load(std::memory_order_relaxed);
-    if (bytes) *bytes = g_moved.load(std::memory_order_relaxed);
-}
+void launch_traffic(long long* launches, long long* bytes) { g_gf_log.traffic(launches, bytes); }
+
+int last_launch(int* v, int cap) { return g_gf_log.last_launch(v, cap); }
 
 // Launch histogram (ecg_launch_histogram): one counter per kernel instantiation launch_gf can dispatch, bumped
 // where the instantiation is picked -- one relaxed add per kernel launch, beside the two above.  Slot layout:
@@ -834,32 +746,14 @@ static void hist_byte(int mode, int binary, int MT) {  // mode: INLINE (also for
 }
 
 static void hist_lat(int binary, int MT, int k, long long B) {  // the bucket of pick_lat_k, EAGER of lat_dword_launch
-    const int kb = k <= 4 ? 0 : k <= 6 ? 1 : k <= 8 ? 2 : k <= 10 ? 3 : k <= 12 ? 4 : 5;
-    g_hist[ECG_HIST_LAT + ((((binary ? 1 : 0) * 8 + (MT - 1)) * 6 + kb) * 2 + (B <= kLatEagerBytes ? 1 : 0))].fetch_add(
-        1, std::memory_order_relaxed);
+    static_assert(kLatBucketCount == 6, "ECG_HIST_LAT slots hold 6 buckets");
+    g_hist[ECG_HIST_LAT + ((((binary ? 1 : 0) * 8 + (MT - 1)) * 6 + lat_bucket(k)) * 2 + (B <= kLatEagerBytes ? 1 : 0))]
+        .fetch_add(1, std::memory_order_relaxed);
 }
 
 int launch_histogram(long long* counts, int cap) {
     for (int i = 0; counts && i < cap && i < ECG_HIST_SLOTS; i++) counts[i] = g_hist[i].load(std::memory_order_relaxed);
     return ECG_HIST_SLOTS;
-}
-
-// Last-launch record (ecg_last_launch; gf_kernels.hpp last_launch names the fields): nine relaxed stores per
-// launch_gf call, as the check libraries' CheckLaunchLog keeps its six.  Diagnostics only: a reader racing a launch
-// may see fields of two launches.
-std::atomic<int> g_last[kGfLaunchFields] = {};
-
-static void record_launch(const GfLaunch& a, int grid_map, int map_group, int cols_per_wg, int wg_per_stripe, int mode,
-                          int kernel) {
-    const int v[kGfLaunchFields] = {grid_map, map_group,   cols_per_wg, wg_per_stripe, a.S,
-                                    a.rtiles, a.row_split, mode,        kernel};
-    for (int i = 0; i < kGfLaunchFields; ++i) g_last[i].store(v[i], std::memory_order_relaxed);
-}
-
-int last_launch(int* v, int cap) {
-    if (v && cap >= kGfLaunchFields)
-        for (int i = 0; i < kGfLaunchFields; ++i) v[i] = g_last[i].load(std::memory_order_relaxed);
-    return kGfLaunchFields;
 }
 
 hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st, int* n_wg) {
@@ -871,42 +765,28 @@ hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st
         (base.S != 1 || base.k > kInlineSrc || base.m > kInlineDst))
         return hipErrorInvalidValue;
     if (base.B == 0) return hipSuccess;
-    init_options();
     GfLaunch a = base;
     const long long vec_bytes = vec_ok ? (a.B & ~15LL) : 0;
-    g_launched.fetch_add((vec_bytes > 0) + (vec_bytes < a.B), std::memory_order_relaxed);
-    g_moved.fetch_add((long long)a.S * a.B * ((long long)a.rtiles * a.k + a.m), std::memory_order_relaxed);
-    if (mode == GF_MODE_INLINE_LAT && vec_bytes == a.B && a.B <= g_opt[ECG_OPT_LAT_DWORD_BYTES].load() &&
+    g_gf_log.count((vec_bytes > 0) + (vec_bytes < a.B), (long long)a.S * a.B * ((long long)a.rtiles * a.k + a.m));
+    if (mode == GF_MODE_INLINE_LAT && vec_bytes == a.B && a.B <= get_option(ECG_OPT_LAT_DWORD_BYTES) &&
         a.k <= kLatMaxSrc && a.rtiles == 1 && a.MT <= kMaxMT) {
         // small zero-copy call: 4 bytes per lane (gf_lat_dword_kernel)
         const long long gx = ((a.B >> 2) + kLatThreads - 1) / kLatThreads;
         Launcher l = a.binary ? pick_lat_dword_bin<true>(a.MT, a.k) : pick_lat_dword_bin<false>(a.MT, a.k);
         if (!l) return hipErrorInvalidValue;
         hist_lat(a.binary, a.MT, a.k, a.B);
-        record_launch(a, 0, 1, kLatThreads, (int)gx, mode, 2);  // gx workgroups of kLatThreads four-byte columns, linear
+        // gx workgroups of kLatThreads four-byte columns, linear
+        g_gf_log.record({0, 1, kLatThreads, (int)gx, a.S, a.rtiles, a.row_split, mode, 2});
         const hipError_t e = l(a, dim3((unsigned)gx), st);
         if (e != hipSuccess) return e;
         if (n_wg) *n_wg = (int)gx;
         return hipSuccess;
     }
+    long long gx = 0;
     if (vec_bytes > 0) {
-        const long long ncols = vec_bytes >> 4;
-        long long cpw = g_opt[ECG_OPT_COLS_PER_WG].load();
-        if (cpw <= 0) cpw = kThreads;  // 2 KiB of every block per workgroup (measured best, r01 microbench)
-        if (ncols < cpw) cpw = ((ncols + kThreads - 1) / kThreads) * kThreads;
-        a.cols_per_wg = (int)cpw;
-        a.wg_per_stripe = (int)((ncols + cpw - 1) / cpw);
-        a.off0 = 0;
-        const long long gx = (long long)a.S * a.wg_per_stripe;
-        if (gx > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-        long long gm = g_opt[ECG_OPT_GRID_MAP].load();
-        if (gm == 3) gm = outputs_in_stripe(a, mode) ? 1 : 2;
-        long long G = g_opt[ECG_OPT_MAP_GROUP].load();
-        while (G > 1 && a.S % (8 * G) != 0) G >>= 1;  // the largest power-of-two divisor run that tiles S
-        if (gm == 2 && a.S % (8 * G) != 0) gm = 1;
-        a.grid_map = (gm == 1 && gx % 8 == 0) ? 1 : (gm == 2) ? 2 : 0;
-        a.map_group = (int)G;
-        const int nt = a.MT > kMaxMT ? 3 : (int)g_opt[ECG_OPT_NT].load();  // wide tiles: built for the default only
+        const hipError_t refused = plan_vector_path(a, vec_bytes, outputs_in_stripe(a, mode) ? 1 : 2, gx);
+        if (refused != hipSuccess) return refused;
+        const int nt = a.MT > kMaxMT ? 3 : (int)get_option(ECG_OPT_NT);  // wide tiles: built for the default only
         Launcher l = nullptr;
         switch (mode) {
             case GF_MODE_INLINE: l = pick_vec<GF_MODE_INLINE>(a, nt); break;
@@ -918,22 +798,15 @@ hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st
         if (!l) return hipErrorInvalidValue;
         if (a.done_flags && (mode != GF_MODE_INLINE_LAT || vec_bytes < a.B)) return hipErrorInvalidValue;
         hist_vec(mode, a.binary, nt, a.MT);
-        record_launch(a, a.grid_map, a.map_group, a.cols_per_wg, a.wg_per_stripe, mode, 0);
+        g_gf_log.record({a.grid_map, a.map_group, a.cols_per_wg, a.wg_per_stripe, a.S, a.rtiles, a.row_split, mode, 0});
         const hipError_t e = l(a, dim3((unsigned)gx, (unsigned)a.rtiles), st);
         if (e != hipSuccess) return e;
         if (n_wg) *n_wg = (int)(gx * a.rtiles);
     }
     if (a.done_flags && vec_bytes < a.B) return hipErrorInvalidValue;  // the byte kernel posts no flags
     if (vec_bytes < a.B) {
-        const long long nbytes = a.B - vec_bytes;
-        long long bpw = 16LL * kThreads;
-        if (nbytes < bpw) bpw = ((nbytes + kThreads - 1) / kThreads) * kThreads;
-        a.cols_per_wg = (int)bpw;
-        a.wg_per_stripe = (int)((nbytes + bpw - 1) / bpw);
-        a.off0 = vec_bytes;
-        a.grid_map = 0;
-        const long long gx = (long long)a.S * a.wg_per_stripe;
-        if (gx > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+        const hipError_t refused = plan_byte_path(a, vec_bytes, gx);
+        if (refused != hipSuccess) return refused;
         Launcher l = nullptr;
         switch (mode) {
             case GF_MODE_INLINE:
@@ -945,7 +818,7 @@ hipError_t launch_gf(const GfLaunch& base, int mode, bool vec_ok, hipStream_t st
         if (!l) return hipErrorInvalidValue;
         hist_byte(mode == GF_MODE_INLINE_LAT ? (int)GF_MODE_INLINE : mode, a.binary, a.MT);
         if (vec_bytes == 0)  // the byte kernel alone: cols_per_wg counts bytes, the map is linear
-            record_launch(a, 0, 1, a.cols_per_wg, a.wg_per_stripe, mode, 1);
+            g_gf_log.record({0, 1, a.cols_per_wg, a.wg_per_stripe, a.S, a.rtiles, a.row_split, mode, 1});
         const hipError_t e = l(a, dim3((unsigned)gx, (unsigned)a.rtiles), st);
         if (e != hipSuccess) return e;
     }
@@ -965,27 +838,6 @@ hipError_t launch_fill_splitmix(void* dst, long long nbytes, unsigned long long 
     if (blocks > 8192) blocks = 8192;
     return launch_kernel(fill_splitmix_kernel, dim3((unsigned)blocks), dim3(kThreads), st, (uint8_t*)dst, nbytes,
                          seed, word_offset);
-}
-
-void make_coef_tab(int c, CoefTab* t) {
-    c &= 0xff;
-    uint8_t e0[8], e1[8], e2[4];
-    for (int e = 0; e < 8; ++e) {
-        e0[e] = (uint8_t)gf::mul(c, e);
-        e1[e] = (uint8_t)gf::mul(c, e << 3);
-    }
-    for (int e = 0; e < 4; ++e) e2[e] = (uint8_t)gf::mul(c, e << 6);
-    auto pack = [](const uint8_t* b) {
-        return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-    };
-    t->t0lo = pack(e0);
-    t->t0hi = pack(e0 + 4);
-    t->t1lo = pack(e1);
-    t->t1hi = pack(e1 + 4);
-    t->t2 = pack(e2);
-    t->mask = (c == 1) ? 0xffffffffu : 0u;
-    t->pad0 = 0u;
-    t->pad1 = 0u;
 }
 
 }  // namespace ecg

@@ -133,7 +133,7 @@ void launch_traffic(long long* launches, long long* bytes);
 int launch_histogram(long long* counts, int cap);
 // Geometry of this process's most recent launch_gf call as placed in the descriptor after the fallbacks (include/ecg.h
 // ecg_last_launch; all zero before the first): grid_map, map_group, cols_per_wg, wg_per_stripe, S, rtiles -- the six
-// fields of the check libraries' records (check_launch.hpp) --, then row_split, mode (GfMode) and kernel (0: the call
+// fields of the check libraries' records (launch_rule.hpp) --, then row_split, mode (GfMode) and kernel (0: the call
 // ran a vector launch, which the geometry then describes; 1: the byte kernel only; 2: the latency kernel).  Returns
 // the field count; v is written when cap suffices.
 constexpr int kGfLaunchFields = 9;

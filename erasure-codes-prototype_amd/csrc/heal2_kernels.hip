@@ -27,7 +27,7 @@
 // Workgroups own disjoint chunks of a stripe, lanes disjoint columns: as long as the launch's stripe ids are distinct
 // no two lanes read-modify-write the same bytes.
 #include "check_device.hpp"
-#include "check_launch.hpp"
+#include "launch_rule.hpp"
 #include "heal2_kernels.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -262,7 +262,7 @@ __global__ void __launch_bounds__(kThreads) gf_heal2_byte_kernel(const Heal2Laun
 // ---------------------------------------------------------------------------------------------
 // Dispatch
 
-struct Heal2Kernels {  // check_launch.hpp candidate_kernel
+struct Heal2Kernels {  // launch_rule.hpp candidate_kernel
     template <int R, int MODE, bool BYTE>
     static const void* kernel() {
         if constexpr (BYTE) return (const void*)gf_heal2_byte_kernel<R, MODE>;

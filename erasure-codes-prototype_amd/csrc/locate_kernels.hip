@@ -23,7 +23,7 @@
 // atomic instructions -- none when they are all zero: a clean stripe writes nothing.  No LDS, no barrier.
 // Integer adds commute: the counts are exact and reproducible.
 #include "check_device.hpp"
-#include "check_launch.hpp"
+#include "launch_rule.hpp"
 #include "locate_kernels.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(kThreads) gf_locate_byte_kernel(const LocateLa
 // ---------------------------------------------------------------------------------------------
 // Dispatch
 
-struct LocateKernels {  // check_launch.hpp candidate_kernel
+struct LocateKernels {  // launch_rule.hpp candidate_kernel
     template <int R, int MODE, bool BYTE>
     static const void* kernel() {
         if constexpr (BYTE) return (const void*)gf_locate_byte_kernel<R, MODE>;

@@ -39,7 +39,7 @@ hipError_t launch_locate(const LocateLaunch& base, int mode, bool vec_ok, hipStr
 // Locate kernels launched in this process, and the bytes they read as planned (S * B * n: every block once).
 void locate_traffic(long long* launches, long long* bytes);
 // Geometry of this process's most recent vector-path launch, as placed in its descriptor after the fallbacks
-// (check_launch.hpp CheckLaunchLog): grid_map, map_group, cols_per_wg, wg_per_stripe, S, rtiles (all zero before the
+// (launch_rule.hpp CheckLaunchLog): grid_map, map_group, cols_per_wg, wg_per_stripe, S, rtiles (all zero before the
 // first).  Returns the field count; v is written when cap suffices.  A diagnostic for tests: it says which
 // workgroup -> chunk map a call ran.
 int locate_last_launch(int* v, int cap);

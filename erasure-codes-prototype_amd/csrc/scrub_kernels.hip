@@ -5,7 +5,7 @@
 // The data path is the region product's (gf_kernels.hip; shared pieces in gf_device.hpp, and check_device.hpp for what
 // the locate and the heal share with this file): one lane per 16-byte column, non-temporal dwordx4 loads, CoefTab
 // tables in SGPRs, the same folds into MT accumulators, the same load batches (check_device.hpp fold_inputs),
-// workgroup -> chunk maps (check_launch.hpp) and occupancy hints.  Where the product stores its accumulators, the
+// workgroup -> chunk maps (launch_rule.hpp) and occupancy hints.  Where the product stores its accumulators, the
 // check counts their nonzero bytes into MT per-lane counters (4 VALU ops per dword against ~18 per coefficient
 // for the fold); a wave whose counters are all zero is done, any other reduces them with shuffles and issues at
 // most one device-scope atomic add per row -- none where the sum is zero, so a clean stripe reads every byte
@@ -13,7 +13,7 @@
 // An encode-shaped check, H = [C | I], folds only C through the tables; row q's stored block is XORed in by one
 // v_bitop3 per dword (ScrubLaunch::ident): the check then costs the encode's arithmetic, not (k + m) / k of it.
 #include "check_device.hpp"
-#include "check_launch.hpp"
+#include "launch_rule.hpp"
 #include "scrub_kernels.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)

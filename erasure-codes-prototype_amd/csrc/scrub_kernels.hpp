@@ -26,7 +26,7 @@ hipError_t launch_scrub(const ScrubLaunch& base, int mode, bool vec_ok, hipStrea
 // for the identity part of an encode-shaped check).
 void scrub_traffic(long long* launches, long long* bytes);
 // Geometry of this process's most recent vector-path launch, as placed in its descriptor after the fallbacks
-// (check_launch.hpp CheckLaunchLog): grid_map, map_group, cols_per_wg, wg_per_stripe, S, rtiles (all zero before the
+// (launch_rule.hpp CheckLaunchLog): grid_map, map_group, cols_per_wg, wg_per_stripe, S, rtiles (all zero before the
 // first).  Returns the field count; v is written when cap suffices.  A diagnostic for tests: it says which
 // workgroup -> chunk map a call ran.
 int scrub_last_launch(int* v, int cap);

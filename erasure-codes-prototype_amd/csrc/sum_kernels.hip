@@ -22,7 +22,7 @@
 // ladder per lane: slow, and correct.
 #include <string.h>
 
-#include "check_launch.hpp"
+#include "launch_rule.hpp"
 #include "sum_kernels.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -239,18 +239,13 @@ const void* pick(int mode, bool byte, int scheme) {
     return nullptr;
 }
 
-CheckLaunchLog g_sum_log;  // its counters; the last-launch record below has this library's own fields
-std::atomic<int> g_sum_last[kSumLaunchFields]{};
+LaunchLog<kSumLaunchFields> g_sum_log;  // the record has this library's own fields (sum_kernels.hpp)
 
 }  // namespace
 
 void sum_traffic(long long* launches, long long* bytes) { g_sum_log.traffic(launches, bytes); }
 
-int sum_last_launch(int* v, int cap) {
-    if (v && cap >= kSumLaunchFields)
-        for (int i = 0; i < kSumLaunchFields; ++i) v[i] = g_sum_last[i].load(std::memory_order_relaxed);
-    return kSumLaunchFields;
-}
+int sum_last_launch(int* v, int cap) { return g_sum_log.last_launch(v, cap); }
 
 hipError_t launch_sum(int mode, int n, const int* src_ids, const uint8_t* const* ptrs, const void* base,
                       long long sstride, long long bstride, long long B, const int* d_stripe_of, int S,
@@ -314,8 +309,7 @@ hipError_t launch_sum(int mode, int n, const int* src_ids, const uint8_t* const*
             a.seg_bytes = seg;
             a.segs = (int)vsegs;
             const long long gx = blocks * a.segs;
-            const int geo[kSumLaunchFields] = {0, (int)seg, a.segs, S * n, scheme};
-            for (int f = 0; f < kSumLaunchFields; ++f) g_sum_last[f].store(geo[f], std::memory_order_relaxed);
+            g_sum_log.record({0, (int)seg, a.segs, S * n, scheme});
             if (const hipError_t e = launch_kernel(pick(mode, false, scheme), a, dim3((unsigned)gx), st); e != hipSuccess)
                 return e;
             a.affine = 0u;
@@ -326,10 +320,7 @@ hipError_t launch_sum(int mode, int n, const int* src_ids, const uint8_t* const*
             a.seg_bytes = bpw;
             a.segs = (int)bsegs;
             const long long gx = blocks * a.segs;
-            if (vec_bytes == 0) {
-                const int geo[kSumLaunchFields] = {1, (int)bpw, a.segs, S * n, 0};
-                for (int f = 0; f < kSumLaunchFields; ++f) g_sum_last[f].store(geo[f], std::memory_order_relaxed);
-            }
+            if (vec_bytes == 0) g_sum_log.record({1, (int)bpw, a.segs, S * n, 0});
             if (const hipError_t e = launch_kernel(pick(mode, true, 0), a, dim3((unsigned)gx), st); e != hipSuccess)
                 return e;
         }

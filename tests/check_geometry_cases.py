@@ -3,7 +3,7 @@ tests/test_gpu_check_geometry.py and the wide-check tests of tests/test_gpu_scru
 numpy only, imports nothing of the project).
 
 Geometry.  `expected_geometry` mirrors the host rule of launch_scrub / launch_locate / launch_heal
-(csrc/check_launch.hpp plan_vector_path, the one copy all three call), which turns the options ECG_OPT_GRID_MAP,
+(csrc/launch_rule.hpp plan_vector_path, the one copy all three call), which turns the options ECG_OPT_GRID_MAP,
 ECG_OPT_MAP_GROUP and ECG_OPT_COLS_PER_WG into the launch descriptor's grid_map, map_group, cols_per_wg and
 wg_per_stripe.  GEOMETRY_CASES lists launches that between them take every branch of wg_coords
 (gf_device.hpp) and the column loops for one, two and three iterations; `last_launch()` of either library must
@@ -29,7 +29,7 @@ WAVE_BYTES = 16 * 64             # one wave's 64 columns
 
 def expected_geometry(S, B, grid_map, map_group, cols_per_wg):
     """{grid_map, map_group, cols_per_wg, wg_per_stripe, S} of the vector-path launch over S stripes of B bytes with
-    the three options set as given (csrc/check_launch.hpp plan_vector_path, which launch_scrub, launch_locate and
+    the three options set as given (csrc/launch_rule.hpp plan_vector_path, which launch_scrub, launch_locate and
     launch_heal call when vec_bytes > 0)."""
     ncols = (B & ~15) >> 4                                   # const long long ncols = vec_bytes >> 4;
     cpw = cols_per_wg                                        # long long cpw = get_option(ECG_OPT_COLS_PER_WG);

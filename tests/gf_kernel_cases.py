@@ -24,7 +24,7 @@ NT_POLICIES = (0, 1, 2, 3)        # gf_kernels.hip pick_vec: switch (nt & 3)
 WIDE_BIN_NT = 3                   # gf_kernels.hip gen_pick: `if constexpr (BIN && NT == 3)` builds MT 9..16;
                                   # launch_gf: `nt = a.MT > kMaxMT ? 3 : ...`
 BYTE_MODES = (MODE_INLINE, MODE_PTRS, MODE_STRIDED)  # gf_kernels.hip launch_gf: INLINE_LAT tails run pick_byte<INLINE>
-LAT_DWORD_DEFAULT = 1 << 20       # gf_kernels.hip init_options: ECG_OPT_LAT_DWORD_BYTES
+LAT_DWORD_DEFAULT = 1 << 20       # gf_host.cpp init_options: ECG_OPT_LAT_DWORD_BYTES
 # kernels of the code object outside the enumeration
 OTHER_KERNELS = ("gf_call_worker_kernel", "fill_splitmix_kernel")
 

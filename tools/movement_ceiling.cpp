@@ -14,7 +14,8 @@
 // Build (after `make -C erasure-codes-prototype_amd`; host-only source, linked with the library's kernel object):
 //   hipcc -O2 -std=c++17 -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ierasure-codes-prototype_amd/csrc \
 //     -c tools/movement_ceiling.cpp -o /tmp/mc.o
-//   hipcc --offload-arch=gfx950 /tmp/mc.o erasure-codes-prototype_amd/build/gf_kernels.o -o tools/movement_ceiling
+//   hipcc --offload-arch=gfx950 /tmp/mc.o erasure-codes-prototype_amd/build/gf_kernels.o \
+//     erasure-codes-prototype_amd/build/gf_host.o -o tools/movement_ceiling
 // Run: tools/movement_ceiling [rounds=3] [reps=10] [stripes=4096] [case-name filter] [maps]
 //   maps: the first selected case under grid maps 1 / 2 (G = 1, 16, 64, 128) / 0, interleaved round by round
 // Knobs of the launch (read by the library at first use): ECG_GRID_MAP, ECG_MAP_GROUP, ECG_COLS_PER_WG, ECG_NT.

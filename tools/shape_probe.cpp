@@ -6,7 +6,8 @@
 // Build (after `make -C erasure-codes-prototype_amd`):
 //   hipcc -O2 -std=c++17 -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ierasure-codes-prototype_amd/csrc \
 //     -c tools/shape_probe.cpp -o /tmp/sp.o
-//   hipcc --offload-arch=gfx950 /tmp/sp.o erasure-codes-prototype_amd/build/gf_kernels.o -o tools/shape_probe
+//   hipcc --offload-arch=gfx950 /tmp/sp.o erasure-codes-prototype_amd/build/gf_kernels.o \
+//     erasure-codes-prototype_amd/build/gf_host.o -o tools/shape_probe
 // Run: tools/shape_probe rounds reps case... ; case = k,m,bin,S[,label] (bin 1 = BINARY, every mask ~0; 0 = GENERAL,
 // random non-zero coefficients).  Settings are fixed below; each case runs under each setting every round.
 #include <hip/hip_runtime.h>
