@@ -64,7 +64,8 @@
  * Links against libecg.so (include/ecg.h): same status codes, coefficient-table cache, batch scopes and streams.
  * All pointers are DEVICE pointers unless noted; `stream` is a hipStream_t (NULL = default stream) and the calls are
  * asynchronous on it.  A call flushes the thread's batch scope first (it sees the recorded calls' results).  No call
- * allocates.  Checksums (ecg_sum.h, ecg_psum.h) are not updated: re-sum the touched stripes.
+ * allocates.  Checksums (ecg_sum.h, ecg_psum.h) are not updated: re-sum the touched stripes, or carry the recorded sums
+ * through the same records from delta alone with ecg_usum.h.
  */
 #ifndef ECG_UPDATE_H
 #define ECG_UPDATE_H
