@@ -5,15 +5,14 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
-#include <utility>
 #include <vector>
 
 #include "../../include/ecg_dread.h"
 #include "capi_handle.hpp"
 #include "check_common.hpp"
 #include "dread_kernels.hpp"
+#include "dread_records.hpp"
 #include "engine.hpp"
 #include "gf256.hpp"
 
@@ -166,28 +165,6 @@ int host_plan(int n, int r, const int* H, const unsigned char* lost, int col, un
     return kDreadAnswered;
 }
 
-// The state of a record on the host: the device's rule for states 1-5 (dread_kernels.hip).
-int record_state(const long long* r, int n, long long B, int S, long long max_len, long long out_bytes) {
-    const long long stripe = r[0], col = r[1], off = r[2], len = r[3], out_off = r[4];
-    if (stripe < 0 || stripe >= S) return kDreadBadStripe;
-    if (col < 0 || col >= n) return kDreadBadCol;
-    if (off < 0 || len < 0 || off > B || len > B - off) return kDreadBadRange;
-    if (len > max_len) return kDreadTooLong;
-    if (out_off < 0 || out_off > out_bytes || len > out_bytes - out_off) return kDreadBadOut;
-    return kDreadAnswered;
-}
-
-// [lo, hi) into a set of pairwise disjoint ranges keyed by lo: false if it overlaps one of them.
-typedef std::map<long long, long long> RangeSet;
-bool insert_disjoint(RangeSet& set, long long lo, long long hi) {
-    if (hi <= lo) return true;  // an empty range overlaps nothing
-    auto next = set.lower_bound(lo);
-    if (next != set.end() && next->first < hi) return false;
-    if (next != set.begin() && std::prev(next)->second > lo) return false;
-    set[lo] = hi;
-    return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -252,22 +229,10 @@ int ecg_dread_check_records(const long long* h_records, int R, int n, long long 
                             long long out_bytes) {
     if (R < 0) return refuse("negative size (R = " + num(R) + ")");  // ECG_EINVAL is -2: no record index, not -1
     if (!h_records && R > 0) return refuse("h_records is NULL");
-    static const char* const rule[] = {"", "stripe is not in [0, S)", "col is not in [0, n)",
-                                       "off < 0, len < 0 or off + len > B", "len > max_len",
-                                       "out_off < 0 or out_off + len > out_bytes"};
-    RangeSet outs;
-    for (int i = 0; i < R; i++) {
-        const long long* r = h_records + (size_t)i * kDreadRecordWords;
-        if (const int st = record_state(r, n, B, S, max_len, out_bytes); st != kDreadAnswered) {
-            set_last_error("dread: record " + num(i) + " is refused with state " + num(st) + ": " + rule[st]);
-            return i;
-        }
-        if (!insert_disjoint(outs, r[4], r[4] + r[3])) {
-            set_last_error("dread: record " + num(i) + " overlaps an earlier record's out range");
-            return i;
-        }
-    }
-    return -1;
+    std::string why;
+    const int first = dread_check_records(h_records, R, n, B, S, max_len, out_bytes, why);
+    if (first >= 0) set_last_error("dread: " + why);
+    return first;
 }
 
 int ecg_dread_counters(long long* launches, long long* records) {

@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include "launch_rule.hpp"
+#include "psum_device.hpp"
 #include "psum_kernels.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -38,44 +39,9 @@ namespace ecg {
 
 namespace {
 
-static_assert(kPsumRowBytes == 16 * kThreads, "a row is one dwordx4 per lane");
-static_assert(kThreads == 128, "two waves per row: the tree's level 6 is the step from wave 0 to the row's end");
 static_assert(kPsumMinPiece % kPsumRunBytes == 0, "a byte-path run never straddles two pieces");
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// ---- compile-time tables
-
-constexpr int kTabDword = 0, kTabLevel0 = 1, kTabLevel6 = 7, kTabRow = 8;
-
-constexpr uint32_t table_multiplier(int k) {
-    if (k == kTabDword) return crc_shift(kCrcOne, 4, kCrcPowers.p);
-    if (k == kTabRow) return crc_shift(kCrcOne, kPsumRowBytes, kCrcPowers.p);
-    return crc_shift(kCrcOne, 16ull << (k - kTabLevel0), kCrcPowers.p);
-}
-
-// t[(k * 4 + b) * 256 + v] = (v << 8 b) * multiplier k.  Linear in v: built from the 32 single bits.
-struct PsumTables {
-    uint32_t t[kPsumTablesRows * kPsumTableWords];
-};
-constexpr PsumTables make_tables() {
-    PsumTables r{};
-    for (int k = 0; k < kPsumTablesRows; ++k) {
-        const uint32_t m = table_multiplier(k);
-        for (int b = 0; b < 4; ++b) {
-            uint32_t* t = r.t + (k * 4 + b) * 256;
-            for (int v = 1; v < 256; ++v) {
-                const int low = v & -v;
-                t[v] = v == low ? crc_mul((uint32_t)v << (8 * b), m) : t[v ^ low] ^ t[low];
-            }
-        }
-    }
-    return r;
-}
-
-__device__ const PsumTables kTables = make_tables();
-
-// ---- device pieces
+// ---- device pieces (the tables and the folds are psum_device.hpp's)
 
 template <int MODE>
 __device__ __forceinline__ const uint8_t* block_ptr(const PsumLaunch& a, int i, int c) {
@@ -100,41 +66,6 @@ __device__ __forceinline__ unsigned* sums_of(const PsumLaunch& a, int i, int c) 
 
 __device__ __forceinline__ u32x4 load_row(const uint8_t* p) {
     return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-}
-
-// The first TABLES tables into LDS, 16 bytes per lane and step.
-template <int TABLES>
-__device__ __forceinline__ void fetch_tables(uint32_t* tab) {
-    for (int e = 4 * (int)threadIdx.x; e < TABLES * kPsumTableWords; e += 4 * kThreads)
-        *reinterpret_cast<u32x4*>(tab + e) = *reinterpret_cast<const u32x4*>(kTables.t + e);
-}
-
-// a * (the multiplier of the table at tab)
-__device__ __forceinline__ uint32_t tmul(const uint32_t* tab, uint32_t a) {
-    return tab[a & 0xffu] ^ tab[256 + ((a >> 8) & 0xffu)] ^ tab[512 + ((a >> 16) & 0xffu)] ^ tab[768 + (a >> 24)];
-}
-
-// The remainder of a lane's 16 bytes from its four dword states.
-__device__ __forceinline__ uint32_t lane_fold(const uint32_t* tab, const uint32_t (&s)[4]) {
-    const uint32_t* const t32 = tab + kTabDword * kPsumTableWords;
-    uint32_t f = tmul(t32, s[0]) ^ s[1];
-    f = tmul(t32, f) ^ s[2];
-    f = tmul(t32, f) ^ s[3];
-    return tmul(t32, f);
-}
-
-// Level d of the tree: the lane 2^d to the left holds the remainder of the 2^d lanes that end there.
-__device__ __forceinline__ uint32_t tree_level(const uint32_t* tab, uint32_t f, int d) {
-    const uint32_t left = (uint32_t)__shfl_up((int)f, 1u << d, 64);
-    return tmul(tab + (kTabLevel0 + d) * kPsumTableWords, left) ^ f;
-}
-
-// state = state * x^(8 * 2048) ^ word for a lane's four chains
-__device__ __forceinline__ void row_step(const uint32_t* tab, uint32_t (&s)[4], const u32x4 w) {
-    const uint32_t* const row = tab + kTabRow * kPsumTableWords;
-    const uint32_t x[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int d = 0; d < 4; ++d) s[d] = tmul(row, s[d]) ^ x[d];
 }
 
 // Vector path, P < 2048: bytes [0, hi) of every block, hi a multiple of 16, every block 16-byte aligned.
